@@ -2,7 +2,15 @@
 """Headline benchmark (BASELINE.json): LZ4 compress GB/s + JPEG DCT Gpixel/s
 on 1..8 MI355X, with % of the HBM roofline and the CPU path timed beside it.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the top-level figure needs and nothing else: it
+synthesises the LZ4 input, runs the W warm-up and K timed compress steps and
+prints the line (value, ms_per_step, the roofline of those steps).  --full adds
+every other line: the LZ4 decoders, the RCCL gather (N > 1), the config-4
+share, the "jpeg" sub-line with its batch / reconstruction / entropy stages,
+and the CPU baselines.  --dump-outputs DIR writes what the last timed step
+produced (dump_outputs()) as DIR/<name>.npy, for comparing two builds.
 
 --gpus N > 1 without a launcher: bench.py starts N rank processes itself
 (torch.distributed.run, one per GPU, before this process touches the GPU)
@@ -19,7 +27,9 @@ Workloads (BASELINE.json configs):
          rand() stream, 1024 / N per rank, no exchange.
 Every rank synthesises its own share in HBM (csrc/synth_dev.hip) from the
 seeded generators; a step is one pass of the hot path over the rank's share
-with inputs resident in HBM.  Rank 0 prints one JSON line.
+with inputs resident in HBM.  Rank 0 prints one JSON line.  The lines below the
+top level ("jpeg", "lz4_decode", "cfg4_share", "cpu_baseline", the gather) are
+measured under --full only and are null in a plain run.
 """
 import argparse
 import datetime
@@ -53,6 +63,7 @@ SPEC_CLOCK_GHZ = 2.4
 CFG4_BYTES = 64 << 30          # configs[3]
 CFG5_IMAGES = 1024             # configs[4]
 W4K, H4K = 3840, 2160
+DUMP_SEED = 20240607           # --dump-outputs: the sampled stream positions
 
 
 def log(*a):
@@ -254,6 +265,13 @@ def main(argv=None):
     ap.add_argument("--jpeg-total-images", type=int, default=0,
                     help="N > 1 workload; default 1024 (configs[4])")
     ap.add_argument("--jpeg-steps", type=int, default=0, help="default: max(50, 10*steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the top-level figure: LZ4 decode, "
+                         "the RCCL gather (N > 1), the config-4 share, the JPEG lines and the "
+                         "CPU baselines (the --no-* options below trim this set)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs as "
+                         "DIR/<name>.npy (float32 / float64, see dump_outputs())")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-jpeg", action="store_true")
     ap.add_argument("--no-cfg4-share", action="store_true",
@@ -273,6 +291,8 @@ def main(argv=None):
                     help="print each rank's (rank, world, local rank, shares) and exit "
                          "without touching the GPU (tests the launcher plumbing)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rc = maybe_self_launch(args, argv)
     if rc is not None:
@@ -308,13 +328,13 @@ def main(argv=None):
     lz4_total, jpeg_total, scaling = workloads(world, args)
 
     line = run_lz4(ctx, lz4_total, scaling)
-    if not args.no_jpeg:
+    if args.full and not args.no_jpeg:
         ctx.phase("jpeg")
         line["jpeg"] = run_jpeg(ctx, jpeg_total, scaling)
     else:
         line["jpeg"] = None
 
-    if rank == 0 and not multi and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not multi and not args.no_cpu_baseline:
         cpu_lz4, cpu_jpeg = cpu_baselines(ctx.host_text, args, ctx.host_img)
         line["cpu_baseline"] = cpu_lz4
         if line["jpeg"] is not None:
@@ -379,7 +399,7 @@ def run_lz4(ctx, n_total, scaling):
     n = hi - lo
     final_shard = hi == n_total
     log(f"rank {rank}: synthesising LZ4 shard [{lo}, {hi}) of {n_total} B in HBM")
-    if rank == 0 and not ctx.multi:
+    if args.full and rank == 0 and not ctx.multi and not args.no_cpu_baseline:
         # bounded host copy for the CPU baseline (the same bytes); made before
         # the device input so that seconds of host work do not sit between the
         # device synthesis and the warm-up steps (the clock ramps back up over
@@ -490,6 +510,122 @@ def run_lz4(ctx, n_total, scaling):
                     "and the rank's own step time before the closing barrier"}
         log(f"lz4 per rank: call ms {per_rank['call_ms']}, step ms {per_rank['step_ms']}")
 
+    if args.dump_outputs:
+        # d_out still holds the last timed step's stream (nothing has run since)
+        dump_outputs(ctx, args.dump_outputs, d_out[1:] if ctx.multi else d_out, out_len)
+    lz4_dec = gather_ms = gather_ok = share = None
+    if args.full:
+        lz4_dec, gather_ms, gather_ok, share = run_lz4_extras(ctx, comp, d_in, d_out, d_len, n,
+                                                              n_total, final_shard)
+
+    roof_lz4 = {
+        "bound": "hbm", "kernel": "lz4_tiles",
+        "achieved": round(n / (avg_match_ms / 1e3) / 1e9, 2), "peak": HBM_PEAK_GBS,
+        "unit": "GB/s", "frac": round(n / (avg_match_ms / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
+        "traffic": measured_traffic("lz4", n, 1 << 30),
+        # HBM bytes of the whole compressor (lz4_tiles + lz4_emit) per call; the
+        # call's algorithmic bytes are 1 B read + ~1.035 B written per input byte
+        "pipeline_traffic": (None if measured_traffic("lz4_emit", n, 1 << 30) is None else
+                             measured_traffic("lz4", n, 1 << 30) +
+                             measured_traffic("lz4_emit", n, 1 << 30)),
+        "binding_roof": issue_roof(n, avg_match_ms),
+        "algorithmic_bytes_per_launch": n,
+        "avg_launch_ms": round(avg_match_ms, 4),
+        "whole_call_ms": round(avg_call_ms, 4),
+        "note": "algorithmic bytes = 1 B read per input byte (SURVEY §8d: the HBM-read "
+                "roofline); achieved = that / lz4_tiles time (summed over its 2^24-block "
+                "launch chunks) from HIP events on its launch stream in each timed step, max "
+                "over ranks; traffic = FETCH_SIZE(x2, gfx950) + WRITE_SIZE per launch from " +
+                os.path.basename(_profile_json(TRAFFIC_JSON)) + "; the kernel is issue-bound "
+                "(DESIGN.md), not HBM-bound",
+    }
+    comp.close()
+    cfg = ("lz4_compress_1GiB_text_per_gpu" if not ctx.multi else
+           "lz4_compress_64GiB_text_sharded_rccl_gather")
+    if not ctx.multi and n != 1 << 30:
+        cfg = f"lz4_compress_{n}B_text_per_gpu"
+    if ctx.multi and n_total != CFG4_BYTES:
+        cfg = f"lz4_compress_{n_total}B_text_sharded_rccl_gather"
+    return {
+        "metric": "LZ4 compress GB/s + JPEG DCT Mpixel/s at 1/2/4/8 MI355X; % HBM roofline",
+        "value": round(lz4_gbs, 3), "unit": "GB/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(lz4_ms, 4),
+        "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "u8",
+        "data": "synthetic: random_extract-style 30000-B passages of Metamorphosis.txt, "
+                "newlines->spaces, glibc rand seed 1; each rank synthesises its shard in HBM",
+        "config": {"workload": cfg, "bytes_per_rank": n, "bytes_total": n_total, "block": 300,
+                   "parallelism": f"shard{world}", "compressed_bytes_total": out_total,
+                   "step": ("compress (stream-ordered: the K calls queue back to back, each "
+                            "call's length read after the timed region)" if not ctx.multi else
+                            "segment compress + length read-back + all_gather of segment "
+                            "lengths (a host round trip per step)")},
+        "roofline": roof_lz4,
+        "cpu_baseline": None,
+        "lz4_gather_ms": None if gather_ms is None else round(gather_ms, 3),
+        "lz4_gather_ok": gather_ok,
+        "lz4_gather_chunk_bytes": ldist.GATHER_CHUNK if ctx.multi else None,
+        "per_rank": per_rank,
+        "value_incl_gather": (None if gather_ms is None else
+                              round(n_total / ((lz4_ms + gather_ms) / 1e3) / 1e9, 3)),
+        "value_per_gpu": round(lz4_gbs / world, 3),
+        "cfg4_share": share,
+        "lz4_decode": lz4_dec,
+    }
+
+
+def dump_outputs(ctx, path, d_stream, length):
+    """--dump-outputs: what the last timed step handed its caller -- the
+    compressed stream in HBM (`length` bytes at d_stream) and that length --
+    as float .npy files under `path`, small enough to keep (about 25 MB):
+      lz4_length.npy             float64 [1]     the stream's length in bytes
+      lz4_stream_chunk_sums.npy  float64 [C, 2]  per 64 KiB chunk of the stream: the sum of
+                                 its bytes and the sum of byte x (1 + offset in the chunk);
+                                 exact in float64, covers every byte of the stream
+      lz4_stream_head.npy        float32 [<= 1 MiB]  the first bytes (frame byte, first blocks)
+      lz4_stream_tail.npy        float32 [<= 1 MiB]  the last bytes (the end mark)
+      lz4_stream_sample.npy      float32 [4 Mi]  the bytes at fixed positions drawn from a
+                                 seeded generator over [0, length)
+    Rank 0 writes these names, rank r > 0 the same with a `.rank<r>` infix.
+    The inputs are seeded, so two runs with the same arguments write equal files."""
+    import numpy as np
+    torch = ctx.torch
+    os.makedirs(path, exist_ok=True)
+    CH, EDGE, NSAMPLE = 1 << 16, 1 << 20, 1 << 22
+    s = d_stream[:length]
+    weight = torch.arange(1, CH + 1, dtype=torch.int64, device=s.device)
+    sums = []
+    for lo in range(0, length, 1024 * CH):          # 64 MiB of the stream at a time
+        part = s[lo:lo + 1024 * CH]
+        nch = (part.numel() + CH - 1) // CH
+        padded = torch.zeros(nch * CH, dtype=torch.int64, device=s.device)
+        padded[:part.numel()] = part
+        padded = padded.view(nch, CH)
+        sums.append(torch.stack([padded.sum(1), (padded * weight).sum(1)], 1))
+    sums = torch.cat(sums) if sums else torch.zeros(0, 2, dtype=torch.int64, device=s.device)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, max(1, length), NSAMPLE))
+    sample = s[torch.from_numpy(idx).to(s.device)] if length else s[:0]
+    out = {
+        "lz4_length": np.array([length], dtype=np.float64),
+        "lz4_stream_chunk_sums": sums.cpu().numpy().astype(np.float64),
+        "lz4_stream_head": s[:EDGE].cpu().numpy().astype(np.float32),
+        "lz4_stream_tail": s[max(0, length - EDGE):].cpu().numpy().astype(np.float32),
+        "lz4_stream_sample": sample.cpu().numpy().astype(np.float32),
+    }
+    infix = f".rank{ctx.rank}" if ctx.rank else ""
+    for name, a in out.items():
+        np.save(os.path.join(path, f"{name}{infix}.npy"), a)
+    log(f"dumped {', '.join(out)} ({sum(a.nbytes for a in out.values())} B) to {path}")
+
+
+def run_lz4_extras(ctx, comp, d_in, d_out, d_len, n, n_total, final_shard):
+    """--full: the LZ4 lines beside the top-level figure, on the buffers of
+    run_lz4: (lz4_decode line, gather ms, gather ok, config-4 share line)."""
+    torch = ctx.torch
+    from lz4jpeg import dist as ldist
+    from lz4jpeg import lz4
+    args, rank, dev = ctx.args, ctx.rank, ctx.dev
+    stream = torch.cuda.current_stream()
+
     # decoder (SURVEY 8f row 1): this rank's blocks -> bytes, in HBM, with the
     # compressor's device-resident block offsets (no host round trip)
     ctx.phase("lz4 decode")
@@ -593,59 +729,7 @@ def run_lz4(ctx, n_total, scaling):
     if not ctx.multi and not args.no_cfg4_share:
         share = run_cfg4_share(ctx, comp)
 
-    roof_lz4 = {
-        "bound": "hbm", "kernel": "lz4_tiles",
-        "achieved": round(n / (avg_match_ms / 1e3) / 1e9, 2), "peak": HBM_PEAK_GBS,
-        "unit": "GB/s", "frac": round(n / (avg_match_ms / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
-        "traffic": measured_traffic("lz4", n, 1 << 30),
-        # HBM bytes of the whole compressor (lz4_tiles + lz4_emit) per call; the
-        # call's algorithmic bytes are 1 B read + ~1.035 B written per input byte
-        "pipeline_traffic": (None if measured_traffic("lz4_emit", n, 1 << 30) is None else
-                             measured_traffic("lz4", n, 1 << 30) +
-                             measured_traffic("lz4_emit", n, 1 << 30)),
-        "binding_roof": issue_roof(n, avg_match_ms),
-        "algorithmic_bytes_per_launch": n,
-        "avg_launch_ms": round(avg_match_ms, 4),
-        "whole_call_ms": round(avg_call_ms, 4),
-        "note": "algorithmic bytes = 1 B read per input byte (SURVEY §8d: the HBM-read "
-                "roofline); achieved = that / lz4_tiles time (summed over its 2^24-block "
-                "launch chunks) from HIP events on its launch stream in each timed step, max "
-                "over ranks; traffic = FETCH_SIZE(x2, gfx950) + WRITE_SIZE per launch from " +
-                os.path.basename(_profile_json(TRAFFIC_JSON)) + "; the kernel is issue-bound "
-                "(DESIGN.md), not HBM-bound",
-    }
-    comp.close()
-    cfg = ("lz4_compress_1GiB_text_per_gpu" if not ctx.multi else
-           "lz4_compress_64GiB_text_sharded_rccl_gather")
-    if not ctx.multi and n != 1 << 30:
-        cfg = f"lz4_compress_{n}B_text_per_gpu"
-    if ctx.multi and n_total != CFG4_BYTES:
-        cfg = f"lz4_compress_{n_total}B_text_sharded_rccl_gather"
-    return {
-        "metric": "LZ4 compress GB/s + JPEG DCT Mpixel/s at 1/2/4/8 MI355X; % HBM roofline",
-        "value": round(lz4_gbs, 3), "unit": "GB/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(lz4_ms, 4),
-        "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "u8",
-        "data": "synthetic: random_extract-style 30000-B passages of Metamorphosis.txt, "
-                "newlines->spaces, glibc rand seed 1; each rank synthesises its shard in HBM",
-        "config": {"workload": cfg, "bytes_per_rank": n, "bytes_total": n_total, "block": 300,
-                   "parallelism": f"shard{world}", "compressed_bytes_total": out_total,
-                   "step": ("compress (stream-ordered: the K calls queue back to back, each "
-                            "call's length read after the timed region)" if not ctx.multi else
-                            "segment compress + length read-back + all_gather of segment "
-                            "lengths (a host round trip per step)")},
-        "roofline": roof_lz4,
-        "cpu_baseline": None,
-        "lz4_gather_ms": None if gather_ms is None else round(gather_ms, 3),
-        "lz4_gather_ok": gather_ok,
-        "lz4_gather_chunk_bytes": ldist.GATHER_CHUNK if ctx.multi else None,
-        "per_rank": per_rank,
-        "value_incl_gather": (None if gather_ms is None else
-                              round(n_total / ((lz4_ms + gather_ms) / 1e3) / 1e9, 3)),
-        "value_per_gpu": round(lz4_gbs / world, 3),
-        "cfg4_share": share,
-        "lz4_decode": lz4_dec,
-    }
+    return lz4_dec, gather_ms, gather_ok, share
 
 
 def run_cfg4_share(ctx, comp):
@@ -710,7 +794,7 @@ def run_jpeg(ctx, total_images, scaling):
     # image k = pixels [k W H, (k + 1) W H)
     d_img = torch.empty(4 * px * B, dtype=torch.uint8, device=dev)
     synth.rand_rgba_device(d_img, i0 * px, px * B, seed=1)
-    if rank == 0 and not ctx.multi:
+    if rank == 0 and not ctx.multi and not args.no_cpu_baseline:
         ctx.host_img = synth.rand_rgba_stream(0, px, 1).reshape(H, W, 4)
     d_coef = torch.empty(B * jpeg.coef_count(W, H), dtype=torch.int16, device=dev)
     jsteps = args.jpeg_steps or (max(50, 10 * args.steps) if B == 1 else max(5, args.steps))

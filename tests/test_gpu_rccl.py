@@ -106,7 +106,8 @@ def test_bench_distributed_path_at_world1(gpu):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr=127.0.0.1", f"--master-port={port}", os.path.join(ROOT, "bench.py"),
            "--gpus", "1", "--dist", "--lz4-total-bytes", str(16 << 20),
-           "--jpeg-total-images", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "--jpeg-total-images", "2", "--steps", "2", "--warmup", "1", "--full",
+           "--no-cpu-baseline"]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)

@@ -21,7 +21,9 @@ LZ4R_HIPFLAGS := -mllvm -amdgpu-sched-strategy=max-ilp
 CFLAGS_HOST := -O2 -fPIC -Wall -std=gnu11 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include
 LIB     := $(PKG)/lz4jpeg/liblz4jpeg.so
 HDRS    := include/lz4r.h include/jpegr.h include/lz4jpeg_compat.h include/lz4jpeg_synth.h \
-           $(CSRC)/jpeg_tables.h
+           $(CSRC)/jpeg_tables.h \
+           $(CSRC)/wave64.h $(CSRC)/lz4r_prof.h $(CSRC)/lz4r_layout.h $(CSRC)/lz4r_tile_lds.h \
+           $(CSRC)/lz4r_tiles.h $(CSRC)/lz4r_matches.h $(CSRC)/lz4r_scan.h $(CSRC)/lz4r_emit.h
 OBJS    := $(B)/lz4r.o $(B)/lz4r_gpudec.o $(B)/jpegr.o $(B)/jpegr_blocks.o $(B)/jpegr_entropy.o \
            $(B)/synth.o $(B)/synth_dev.o \
            $(B)/lz4r_decode.o $(B)/compat.o $(B)/compat_lz4.o
@@ -93,14 +95,14 @@ build/sanitize_main: $(SAN_SRC) include/lz4r.h include/lz4jpeg_synth.h include/l
 	  -o $@ $(SAN_SRC) -lz -lm -lpthread
 
 # micro-benchmarks: SIMD issue rates (tools/issue.sh) and LDS access costs
-tools: tools/variants/valu_rate tools/variants/lds_rate
+tools: tools/ab/valu_rate tools/ab/lds_rate
 
-tools/variants/valu_rate: tools/valu_rate.hip
-	@mkdir -p tools/variants
+tools/ab/valu_rate: tools/valu_rate.hip
+	@mkdir -p tools/ab
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -o $@ $<
 
-tools/variants/lds_rate: tools/lds_rate.hip
-	@mkdir -p tools/variants
+tools/ab/lds_rate: tools/lds_rate.hip
+	@mkdir -p tools/ab
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -Wno-unused-result -o $@ $<
 
 clean:

@@ -27,11 +27,11 @@
 //     word, up to four literal chunks past the window and the next window
 //     are issued together, so the walk waits on memory once per sequence of
 //     up to ~77 literals (a load per chunk, each waited for, cost 1.28 ->
-//     1.18 ms per GiB: tools/r06_r.sh; two chunks instead of four, 1.068 ->
+//     1.18 ms per GiB: profiles/r06_dec_ab.log; two chunks instead of four, 1.068 ->
 //     1.015), longer runs take four chunks per round trip, and each load runs
 //     only on the lanes that need it: the vector memory address unit is the
 //     bound (TA busy ~80 % of the kernel, ~45 cycles per scattered wave load,
-//     tools/r06_w.sh), and a lane with exec off costs it nothing (1.17 ->
+//     profiles/r06_dec_ta_pmc.txt), and a lane with exec off costs it nothing (1.17 ->
 //     1.06 ms per GiB);
 //   - literals move in 16-byte chunks; a match of distance D is copied in
 //     chunks of min(16, d) bytes at a distance d that grows from D (the

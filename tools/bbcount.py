@@ -19,7 +19,7 @@ per SIMD, VOP3-only / SGPR-operand / DPP / VOPC ~4, 64-bit shifts ~5.6).
           corpus (1 GiB, synthesised on the device) with it once, read the
           counters -> <out>/bbcounts.json.
   report  counts x static opcode lists -> dynamic opcodes per 300-B block,
-          the cost-weighted VALU cycles (tools/valu_cost.py classes) and the
+          the cost-weighted VALU cycles (tools/valu_cost.json classes) and the
           per-pipe roof, optionally against a PMC summary.
 """
 import collections

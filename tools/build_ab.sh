@@ -1,17 +1,30 @@
-# Build an A/B variant library from a modified copy of one product source:
-#   tools/build_ab.sh path/to/file.hip name [lz4r|jpegr|...]
-#     -> tools/ab/lib<obj>_<name>.so  (the product objects, with
-#        build/<obj>.o replaced by the variant; default obj: lz4r, lib prefix
-#        liblz4_ for lz4r and libjpeg_ for jpegr)
+# Build an A/B variant library from a modified copy of one product source, a
+# .hip or a header one includes (the copy keeps the product file's name):
+#   tools/build_ab.sh path/to/lz4r_emit.h name          (headers: obj lz4r)
+#   tools/build_ab.sh path/to/jpegr.hip name            (obj: the .hip's name)
+#   tools/build_ab.sh path/to/jpeg_tables.h name jpegr  (a header of another obj)
+#     -> tools/ab/lib<obj>_<name>.so  (the product objects, make lib first, with
+#        build/<obj>.o replaced by the variant; lib prefix liblz4_ for lz4r and
+#        libjpeg_ for jpegr), its device assembly tools/ab/<obj>_<name>.s
+# The variant compiles in a directory of its own, tools/ab/<obj>_<name>/: the
+# product's csrc sources with the one file replaced, so every quoted include
+# finds the variant's files first.
 set -e
 cd "$(dirname "$0")/.."
-obj=${3:-lz4r}
+f=$(basename "$1")
+case $f in *.hip) obj=${3:-${f%.hip}} ;; *) obj=${3:-lz4r} ;; esac
+[ -f lz4-jpeg_amd/csrc/$f ] || { echo "$f: not a file of lz4-jpeg_amd/csrc"; exit 1; }
 case $obj in lz4r) lib=liblz4_$2.so ;; jpegr) lib=libjpeg_$2.so ;; *) lib=lib${obj}_$2.so ;; esac
-mkdir -p tools/ab
-cp "$1" tools/ab/${obj}_$2.hip
-[ $obj = lz4r ] && [ -z "$NO_LZ4R_FLAGS" ] && EXTRA="$EXTRA $(make -s print-LZ4R_HIPFLAGS)"
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fno-strict-aliasing -fPIC -std=c++17 $EXTRA \
-  -I include -I lz4-jpeg_amd/csrc -c tools/ab/${obj}_$2.hip -o tools/ab/${obj}_$2.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o tools/ab/$lib \
-  tools/ab/${obj}_$2.o $(ls lz4-jpeg_amd/build/*.o | grep -v -e "/$obj.o" -e _seq.o -e _par.o -e png_io.o)
+D=tools/ab/${obj}_$2
+rm -rf $D
+mkdir -p $D
+cp lz4-jpeg_amd/csrc/*.h lz4-jpeg_amd/csrc/$obj.hip $D/
+cp "$1" $D/$f
+HIPCC=$(make -s print-HIPCC)
+FLAGS="$(make -s print-HIPFLAGS) $EXTRA"
+[ $obj = lz4r ] && [ -z "$NO_LZ4R_FLAGS" ] && FLAGS="$FLAGS $(make -s print-LZ4R_HIPFLAGS)"
+$HIPCC $FLAGS -I lz4-jpeg_amd/csrc -c $D/$obj.hip -o $D/$obj.o
+$HIPCC $FLAGS -I lz4-jpeg_amd/csrc --cuda-device-only -S $D/$obj.hip -o - | grep -v __hip_cuid_ > tools/ab/${obj}_$2.s
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o tools/ab/$lib \
+  $D/$obj.o $(ls lz4-jpeg_amd/build/*.o | grep -v -e "/$obj.o" -e _seq.o -e _par.o -e png_io.o)
 echo built tools/ab/$lib

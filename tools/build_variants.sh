@@ -1,17 +1,17 @@
-# Build timing-ablation variants of liblz4jpeg.so into tools/variants/ (not shipped).
+# Build the compressor's tools builds into tools/ab/ (not shipped): the
+# product objects (make lib first) with lz4r.o recompiled under one macro each,
+# with the Makefile's own flags for that object.
+#   liblz4_prof.so        -DLZ4R_PROF        per-phase cycles (tools/lz4_prof.py)
+#   liblz4_mark.so        -DLZ4R_MARK        ;PHASE_END markers in the assembly
+#   liblz4_stale_head.so  -DLZ4R_STALE_HEAD  tools/poison_check.sh
 set -e
 cd "$(dirname "$0")/.."
-mkdir -p tools/variants
-for v in "$@"; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fno-strict-aliasing -fPIC -std=c++17 $EXTRA -DLZ4R_VARIANT=$v \
-    -c lz4-jpeg_amd/csrc/lz4r.hip -o tools/variants/lz4r_v$v.o
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o tools/variants/liblz4_v$v.so \
-    tools/variants/lz4r_v$v.o $(ls lz4-jpeg_amd/build/*.o | grep -v -e "/lz4r.o" -e _seq.o -e png_io.o)
-done
-# profiled builds: PROF="0 1" -> liblz4_p0.so, liblz4_p1.so (LZ4R_PROF + variant)
-for v in $PROF; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fno-strict-aliasing -fPIC -std=c++17 -DLZ4R_PROF -DLZ4R_VARIANT=$v \
-    -c lz4-jpeg_amd/csrc/lz4r.hip -o tools/variants/lz4r_p$v.o
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o tools/variants/liblz4_p$v.so \
-    tools/variants/lz4r_p$v.o $(ls lz4-jpeg_amd/build/*.o | grep -v -e "/lz4r.o" -e _seq.o -e png_io.o)
+mkdir -p tools/ab
+HIPCC=$(make -s print-HIPCC)
+FLAGS="$(make -s print-HIPFLAGS) $(make -s print-LZ4R_HIPFLAGS)"
+for v in prof mark stale_head; do
+  $HIPCC $FLAGS -DLZ4R_$(echo $v | tr a-z A-Z) -c lz4-jpeg_amd/csrc/lz4r.hip -o tools/ab/lz4r_$v.o
+  $HIPCC --offload-arch=gfx950 -shared -fPIC -o tools/ab/liblz4_$v.so \
+    tools/ab/lz4r_$v.o $(ls lz4-jpeg_amd/build/*.o | grep -v -e "/lz4r.o" -e _seq.o -e _par.o -e png_io.o)
+  echo built tools/ab/liblz4_$v.so
 done

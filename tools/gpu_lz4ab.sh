@@ -1,5 +1,5 @@
 # LZ4 compressor A/B on the GPU box: for the product build and each variant
-# tools/variants/liblz4_<v>.so given as an argument: the LZ4 parity tests
+# tools/ab/liblz4_<v>.so given as an argument: the LZ4 parity tests
 # (variants only; not slow), 1 GiB timing (medians of 12 calls) and PMC
 # instruction counts per block of lz4_tiles plus the per-kernel durations.
 set -o pipefail
@@ -39,7 +39,7 @@ PY
 }
 run product $PWD/lz4-jpeg_amd/lz4jpeg/liblz4jpeg.so || exit 1
 for v in "$@"; do
-  L=$PWD/tools/variants/liblz4_$v.so
+  L=$PWD/tools/ab/liblz4_$v.so
   LZ4JPEG_LIB=$L timeout -k 10 400 python -m pytest tests/test_gpu_lz4.py tests/test_gpu_decode.py tests/test_gpu_compat.py -x -q -m "gpu and not slow" > $O/t_$v.log 2>&1 || { echo "tests $v failed"; tail -30 $O/t_$v.log; exit 1; }
   echo "-- $v tests: $(tail -1 $O/t_$v.log)"
   run $v $L || exit 1

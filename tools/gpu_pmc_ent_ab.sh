@@ -1,5 +1,5 @@
 # PMC instruction mix of the luma entropy encoder for the product and each
-# tools/variants/libjpegr_entropy_<v>.so (phase-cut builds), one 4K image.
+# tools/ab/libjpegr_entropy_<v>.so (phase-cut builds), one 4K image.
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
@@ -12,4 +12,4 @@ run() {
   python3 tools/pmc_summary.py $O/$1/run_results.db "entropy_encode_lane<true>" | tail -10
 }
 run product $PWD/lz4-jpeg_amd/lz4jpeg/liblz4jpeg.so || exit 1
-for v in "$@"; do run $v $PWD/tools/variants/libjpegr_entropy_$v.so || exit 1; done
+for v in "$@"; do run $v $PWD/tools/ab/libjpegr_entropy_$v.so || exit 1; done

@@ -1,5 +1,5 @@
 """Per-phase cycle shares of lz4_tiles from an LZ4R_PROF build
-(tools/build_variants.sh with PROF=0): run the 1 GiB corpus once to warm up,
+(tools/build_variants.sh: tools/ab/liblz4_prof.so): run the 1 GiB corpus once to warm up,
 then `reps` calls, and print the summed s_memtime cycles of each phase."""
 import ctypes
 import os

@@ -1,11 +1,10 @@
 # The corrupt-head error path of lz4_tiles: a tools build
-# (LZ4R_VARIANT=20) plants one stale, forward-pointing bucket head in every
+# (-DLZ4R_STALE_HEAD) plants one stale, forward-pointing bucket head in every
 # block.  The walk must still end (chains strictly decrease) and the call must
-# return LZ4R_ERR_CORRUPT, not hang.  Built here by tools/build_variants.sh 20.
+# return LZ4R_ERR_CORRUPT, not hang.  Built by tools/build_variants.sh.
 set -o pipefail
 cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out/poison
-LZ4JPEG_LIB=$PWD/tools/variants/liblz4_v20.so timeout -k 10 120 python3 - <<'PY' 2>&1 | tee gpurun_out/poison/poison.log
+LZ4JPEG_LIB=$PWD/tools/ab/liblz4_stale_head.so timeout -k 10 120 python3 - <<'PY' 2>&1
 import os, sys, time
 sys.path[:0] = [os.path.join(os.environ["GRAFT_REPO_ROOT"], "lz4-jpeg_amd")]
 import torch

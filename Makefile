@@ -18,12 +18,17 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -ffp-contract=off -fno-strict-aliasing -f
 # lz4r.hip (the compressor): the max-ILP machine scheduler, -0.3 % lz4_tiles and
 # call time in three in-process A/B orders (tools/ab_inproc.py)
 LZ4R_HIPFLAGS := -mllvm -amdgpu-sched-strategy=max-ilp
+# lz4r_gpudec.hip (the block decoder): the max-memory-clause scheduler, -0.45 %
+# (tools/ab_dec_inproc.py)
+LZ4R_GPUDEC_HIPFLAGS := -mllvm -amdgpu-sched-strategy=max-memory-clause
 CFLAGS_HOST := -O2 -fPIC -Wall -std=gnu11 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include
 LIB     := $(PKG)/lz4jpeg/liblz4jpeg.so
 HDRS    := include/lz4r.h include/jpegr.h include/lz4jpeg_compat.h include/lz4jpeg_synth.h \
            $(CSRC)/jpeg_tables.h \
            $(CSRC)/wave64.h $(CSRC)/lz4r_prof.h $(CSRC)/lz4r_layout.h $(CSRC)/lz4r_tile_lds.h \
-           $(CSRC)/lz4r_tiles.h $(CSRC)/lz4r_matches.h $(CSRC)/lz4r_scan.h $(CSRC)/lz4r_emit.h
+           $(CSRC)/lz4r_tiles.h $(CSRC)/lz4r_matches.h $(CSRC)/lz4r_scan.h $(CSRC)/lz4r_emit.h \
+           $(CSRC)/lz4r_dec_layout.h $(CSRC)/lz4r_dec_parse.h $(CSRC)/lz4r_dec_blocks.h \
+           $(CSRC)/lz4r_dec_bare.h
 OBJS    := $(B)/lz4r.o $(B)/lz4r_gpudec.o $(B)/jpegr.o $(B)/jpegr_blocks.o $(B)/jpegr_entropy.o \
            $(B)/synth.o $(B)/synth_dev.o \
            $(B)/lz4r_decode.o $(B)/compat.o $(B)/compat_lz4.o
@@ -43,8 +48,7 @@ $(B)/%.o: $(CSRC)/%.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(B)/lz4r.o: HIPFLAGS += $(LZ4R_HIPFLAGS)
-# the block decoder: the max-memory-clause scheduler, -0.45 % (tools/ab_dec_inproc.py)
-$(B)/lz4r_gpudec.o: HIPFLAGS += -mllvm -amdgpu-sched-strategy=max-memory-clause
+$(B)/lz4r_gpudec.o: HIPFLAGS += $(LZ4R_GPUDEC_HIPFLAGS)
 
 $(B)/%.o: $(HOST)/%.c $(HDRS) $(HOST)/lzj_host.h
 	@mkdir -p $(B)
@@ -87,12 +91,22 @@ SAN_SRC := tests/sanitize/sanitize_main.c tests/sanitize/cpu_matches.c $(HOST)/l
            oracle/lz4_oracle.c oracle/jpeg_oracle.c oracle/jpeg_entropy_oracle.c
 sanitize: build/sanitize_main
 
-build/sanitize_main: $(SAN_SRC) include/lz4r.h include/lz4jpeg_synth.h include/lz4jpeg_compat.h \
-                     $(HOST)/lzj_host.h
+SAN_FLAGS := -O1 -g -ffp-contract=off -fno-omit-frame-pointer \
+             -fsanitize=address,undefined -fno-sanitize-recover=all
+
+# sanitize_main.c's C++ siblings, whichever the tests directory holds
+# (bare_layout.cpp: the decoder's scratch layout; csrc/lz4r_dec_layout.h is
+# plain host C++), each compiled to an object of its own and linked in
+SAN_CXX_OBJ := $(patsubst tests/sanitize/%.cpp,build/san_%.o,$(wildcard tests/sanitize/*.cpp))
+
+build/san_%.o: tests/sanitize/%.cpp $(CSRC)/lz4r_dec_layout.h include/lz4r.h
 	@mkdir -p build
-	$(CC) -O1 -g -std=gnu11 -ffp-contract=off -fno-omit-frame-pointer \
-	  -fsanitize=address,undefined -fno-sanitize-recover=all \
-	  -o $@ $(SAN_SRC) -lz -lm -lpthread
+	$(CXX) $(SAN_FLAGS) -std=c++17 -Wall -c $< -o $@
+
+build/sanitize_main: $(SAN_SRC) $(SAN_CXX_OBJ) include/lz4r.h include/lz4jpeg_synth.h \
+                     include/lz4jpeg_compat.h $(HOST)/lzj_host.h
+	@mkdir -p build
+	$(CC) $(SAN_FLAGS) -std=gnu11 -o $@ $(SAN_SRC) $(SAN_CXX_OBJ) -lz -lm -lpthread
 
 # micro-benchmarks: SIMD issue rates (tools/issue.sh) and LDS access costs
 tools: tools/ab/valu_rate tools/ab/lds_rate

@@ -15,7 +15,8 @@
  *   - the per-block compat API (host/compat_lz4.c: block_encode,
  *     write_output, find_longest_match and its growing block cache) over a
  *     CPU match provider (cpu_matches.c), on 300-B, short and long blocks
- *     (exact-size heap copies), against the oracle's block encoder.
+ *     (exact-size heap copies), against the oracle's block encoder;
+ *   - the bare-stream decoder's scratch layout (bare_layout.cpp, C++).
  * Exit 0 and "sanitize ok" when every check passed.
  */
 #include <stdint.h>
@@ -40,6 +41,7 @@ int jo_entropy_stream(const int16_t *zz, int n, int *rle, int *rle_len, int *nco
 int jo_entropy_decode(const uint8_t *bits, int nbits, int rle_len, int ncodes,
                       const int16_t *tab_val, const uint8_t *tab_len, const uint64_t *tab_code,
                       int n, int16_t *zz);
+int bare_layout_case(void);   /* bare_layout.cpp */
 
 static int fails = 0;
 #define CHECK(c)                                                        \
@@ -244,6 +246,9 @@ int main(int argc, char **argv) {
     free(img);
   }
   free(meta);
+
+  /* ---- the bare-stream decoder's scratch layout (csrc/lz4r_dec_layout.h) ---- */
+  fails += bare_layout_case();
   if (fails) {
     fprintf(stderr, "%d check(s) failed\n", fails);
     return 1;

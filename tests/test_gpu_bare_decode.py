@@ -53,6 +53,24 @@ def test_bare_truncated_match_streams(gpu, oracle):
         assert lz4.decompress_stream(stream) == data, name
 
 
+def test_bare_exact_retry_with_count_read_back_first(gpu, oracle):
+    """The exact retry (a truncated-match stream fails the fast pass) together
+    with an output capacity above anything the stream could decode to, so the
+    offsets array is allocated only after the block count has come back; then
+    the same stream with a tight capacity, which must not see the control
+    words the first call left."""
+    from lz4jpeg import lz4
+    text = golden_inputs.lz4_input("metamorphosis_spaces")[:60_000]
+    data = text + b" " * ((-len(text)) % 300) + golden_inputs.lz4_input("m_eq_2") + text
+    stream = oracle.lz4_compress(data)
+    out = lz4.decompress_stream(stream, cap=300 * (len(stream) // 8 + 8))
+    assert len(out) == len(data)
+    assert out == data
+    out = lz4.decompress_stream(stream, cap=len(data))
+    assert len(out) == len(data)
+    assert out == data
+
+
 def test_bare_seeded_fuzz_via_gpu_compressor(comp):
     import torch
     from lz4jpeg import lz4

@@ -1,6 +1,7 @@
 """ASan + UBSan run of the host C (lz4r_decode.c, png_io.c, synth.c) and the
-oracle restatements: tests/sanitize/sanitize_main.c built by
-`make sanitize`, no GPU needed."""
+oracle restatements, and the bare-stream decoder's scratch
+layout (tests/sanitize/bare_layout.cpp): tests/sanitize/sanitize_main.c built
+by `make sanitize`, no GPU needed."""
 import os
 import subprocess
 
@@ -16,3 +17,6 @@ def test_host_c_and_oracle_under_asan_ubsan(tmp_path):
                        capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode == 0, r.stderr[-4000:]
     assert "sanitize ok" in r.stdout
+    # csrc/lz4r_dec_layout.h against the layout written out in bare_layout.cpp:
+    # 9 chunk counts x 4 offsets-array sizes
+    assert "bare scratch layout ok (36 cases)" in r.stdout

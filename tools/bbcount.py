@@ -38,9 +38,10 @@ NCNT = 1024
 LABEL = re.compile(r"^(\.LBB\d+_\d+):|^; (%bb\.\d+):|^\s*(1):\s*$")
 
 
-def hipflags():
+def hipflags(unit="LZ4R_HIPFLAGS"):
+    """HIPFLAGS + the object's own Makefile variable (default: lz4r.o's)."""
     out = []
-    for v in ("HIPFLAGS", "LZ4R_HIPFLAGS"):        # lz4r.o's flags
+    for v in ("HIPFLAGS", unit):
         out += subprocess.run(["make", "-s", "-C", REPO, f"print-{v}"], check=True,
                               capture_output=True, text=True).stdout.split()
     return [f for f in out if f not in ("-fPIC",)]
@@ -170,12 +171,8 @@ ENC = "_ZN12_GLOBAL__N_119entropy_encode_laneILb"   # + "1EE" (luma) / "0EE" (ch
 
 
 def dec_flags():
-    """lz4r_gpudec.o's flags: HIPFLAGS + its scheduler (the Makefile's target rule)."""
-    base = subprocess.run(["make", "-s", "-C", REPO, "print-HIPFLAGS"], check=True,
-                          capture_output=True, text=True).stdout.split()
-    mk = open(os.path.join(REPO, "Makefile")).read()
-    m = re.search(r"^\$\(B\)/lz4r_gpudec\.o: HIPFLAGS \+= (.*)$", mk, re.M)
-    return [f for f in base if f != "-fPIC"] + (m.group(1).split() if m else [])
+    """lz4r_gpudec.o's flags: HIPFLAGS + its scheduler (LZ4R_GPUDEC_HIPFLAGS)."""
+    return hipflags("LZ4R_GPUDEC_HIPFLAGS")
 
 
 def build(src=None, name="prod", kernel=KERNEL):
@@ -184,7 +181,9 @@ def build(src=None, name="prod", kernel=KERNEL):
     if kernel == DEC:
         src = src or os.path.join(REPO, "lz4-jpeg_amd", "csrc", "lz4r_gpudec.hip")
         name = "dec_" + name
-        L = compile_asm(src, ("-I", os.path.join(REPO, "include")), flags=dec_flags())
+        # (a copy of the .hip elsewhere still finds the lz4r_dec_*.h it includes)
+        L = compile_asm(src, ("-I", os.path.join(REPO, "include"),
+                              "-I", os.path.join(REPO, "lz4-jpeg_amd", "csrc")), flags=dec_flags())
     elif kernel.startswith(ENC):
         src = src or os.path.join(REPO, "lz4-jpeg_amd", "csrc", "jpegr_entropy.hip")
         name = ("enc1_" if kernel.endswith("1EE") else "enc0_") + name

@@ -1,6 +1,7 @@
 # Build an A/B variant library from a modified copy of one product source, a
 # .hip or a header one includes (the copy keeps the product file's name):
 #   tools/build_ab.sh path/to/lz4r_emit.h name          (headers: obj lz4r)
+#   tools/build_ab.sh path/to/lz4r_dec_bare.h name lz4r_gpudec   (a decoder header)
 #   tools/build_ab.sh path/to/jpegr.hip name            (obj: the .hip's name)
 #   tools/build_ab.sh path/to/jpeg_tables.h name jpegr  (a header of another obj)
 #     -> tools/ab/lib<obj>_<name>.so  (the product objects, make lib first, with
@@ -22,7 +23,9 @@ cp lz4-jpeg_amd/csrc/*.h lz4-jpeg_amd/csrc/$obj.hip $D/
 cp "$1" $D/$f
 HIPCC=$(make -s print-HIPCC)
 FLAGS="$(make -s print-HIPFLAGS) $EXTRA"
-[ $obj = lz4r ] && [ -z "$NO_LZ4R_FLAGS" ] && FLAGS="$FLAGS $(make -s print-LZ4R_HIPFLAGS)"
+# the object's own flags: the Makefile variable of its stem (LZ4R_HIPFLAGS,
+# LZ4R_GPUDEC_HIPFLAGS; empty for the others); NO_LZ4R_FLAGS=1 leaves them out
+[ -z "$NO_LZ4R_FLAGS" ] && FLAGS="$FLAGS $(make -s print-$(echo $obj | tr a-z A-Z)_HIPFLAGS)"
 $HIPCC $FLAGS -I lz4-jpeg_amd/csrc -c $D/$obj.hip -o $D/$obj.o
 $HIPCC $FLAGS -I lz4-jpeg_amd/csrc --cuda-device-only -S $D/$obj.hip -o - | grep -v __hip_cuid_ > tools/ab/${obj}_$2.s
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o tools/ab/$lib \

@@ -1,26 +1,32 @@
-# Device-assembly identity of the compressor translation unit (csrc/lz4r.hip and
-# the headers it includes) against a commit: both texts compiled with the
-# Makefile's own flags and --cuda-device-only -S, the __hip_cuid_<hash> lines
-# (a hash of the file's path) dropped, then compared.
-#   tools/isa_gate.sh <commit> [name]       DEFS="-D.." for the working tree,
-#                                           OLD_DEFS="-D.." for the commit (default: DEFS)
+# Device-assembly identity of one translation unit (csrc/<unit>.hip and the
+# headers it includes; default lz4r, the compressor) against a commit: both
+# texts compiled with the Makefile's own flags for that unit (HIPFLAGS + the
+# variable of the unit's stem, LZ4R_HIPFLAGS / LZ4R_GPUDEC_HIPFLAGS) and
+# --cuda-device-only -S, the __hip_cuid_<hash> lines (a hash of the file's
+# path) dropped, then compared.
+#   tools/isa_gate.sh <commit> [name] [unit]   DEFS="-D.." for the working tree,
+#                                              OLD_DEFS="-D.." for the commit (default: DEFS)
+#   tools/isa_gate.sh <commit> gpudec lz4r_gpudec      the decoder
 #   -> build/isa_gate/<name>_{old,new}.s; prints line counts, sha256 and the
 #      kernels' register counts; exit 1 when the two differ
 set -e -o pipefail
 cd "$(dirname "$0")/.."
 rev=$1
 name=${2:-product}
+unit=${3:-lz4r}
 : "${OLD_DEFS=$DEFS}"
 O=build/isa_gate
+src=lz4-jpeg_amd/csrc/$unit.hip
 rm -rf $O/old_tree
 mkdir -p $O/old_tree
-git archive "$rev" include/lz4r.h lz4-jpeg_amd/csrc | tar -x -C $O/old_tree
-FLAGS="$(make -s print-HIPFLAGS) $(make -s print-LZ4R_HIPFLAGS) --cuda-device-only -S"
+git archive "$rev" include lz4-jpeg_amd/csrc | tar -x -C $O/old_tree
+uvar=$(echo "$unit" | tr a-z A-Z)_HIPFLAGS
+FLAGS="$(make -s print-HIPFLAGS) $(make -s print-$uvar) --cuda-device-only -S"
 HIPCC=$(make -s print-HIPCC)
-echo "old: $HIPCC $FLAGS $OLD_DEFS <$rev>/lz4-jpeg_amd/csrc/lz4r.hip"
-$HIPCC $FLAGS $OLD_DEFS $O/old_tree/lz4-jpeg_amd/csrc/lz4r.hip -o - | grep -v __hip_cuid_ > $O/${name}_old.s
-echo "new: $HIPCC $FLAGS $DEFS lz4-jpeg_amd/csrc/lz4r.hip"
-$HIPCC $FLAGS $DEFS lz4-jpeg_amd/csrc/lz4r.hip -o - | grep -v __hip_cuid_ > $O/${name}_new.s
+echo "old: $HIPCC $FLAGS $OLD_DEFS <$rev>/$src"
+$HIPCC $FLAGS $OLD_DEFS $O/old_tree/$src -o - | grep -v __hip_cuid_ > $O/${name}_old.s
+echo "new: $HIPCC $FLAGS $DEFS $src"
+$HIPCC $FLAGS $DEFS $src -o - | grep -v __hip_cuid_ > $O/${name}_new.s
 for s in old new; do
   echo "$s: $(wc -l < $O/${name}_$s.s) lines, sha256 $(sha256sum < $O/${name}_$s.s | cut -c1-64)"
 done

@@ -79,7 +79,12 @@ __device__ __forceinline__ int clamp_u8(int v) {       // JPEG.c:132-139
 // multiply-adds, the quotient by one v_mul_hi_u32_u24 with ceil(2^32 / 1000)
 // (exact for N < 2^18), the remainder by one multiply-add.  A lane whose N is
 // a multiple of 1000 (about 1 in 1000) evaluates the reference's fp64
-// expression, behind a branch taken only when some lane needs it.
+// expression, behind a branch taken only when some lane needs it.  The
+// Cr / Cb quotients stay within 16..239 for every RGB triple, so clamp_u8
+// (kept because the reference has it, JPEG.c:157, 180) can never fire here.
+// Pinned on all 2^24 triples: the fp64 result differs from floor(N / 1000)
+// at 3464 (Y), 102 (Cr) and 35 (Cb) triples, every one a multiple of 1000
+// (tests/test_jpeg_exact_inputs.py; the kernel: tests/test_gpu_jpeg_exact.py).
 __device__ __forceinline__ uint32_t div1000(uint32_t N) {       // N < 2^18
   return (uint32_t)(((uint64_t)N * 4294968u) >> 32);
 }
@@ -132,6 +137,17 @@ __device__ __forceinline__ void convert_pixel(uint32_t p, bool valid, int r,
 // per-lane flag arithmetic), and the fallback runs behind one wave-uniform
 // branch, so the division sequence runs only when some lane of the wave
 // needs it.
+//
+// Pinned by tests/test_gpu_jpeg_exact.py on tiles 128 + d + a P (P a basis
+// sign pattern of (4,0), (0,4) or (4,4)), whose luma quotients lie a few ulp
+// on either side of nonzero integers.  Without the fallback 27 coefficients
+// of that image come out one too large.  In all 27, and in all 581 such
+// cases over every d and a, r is exactly an integer and coef / T just below
+// it: a band of width zero (exact integers only) gives the same output on
+// that family, so the fast path is more accurate than the ~4 ulp bound above
+// allows for, and the 2^-30 is margin that no known input needs.  Chroma
+// reaches the band only with near-zero residues there (no 8 x 4 coefficient
+// of those tiles is near a nonzero multiple of its step).
 template <int W>
 __device__ __forceinline__ void quantize_row(const double (&sm)[W], const double *K,
                                              const double *aa, const int *T, int (&q)[W]) {
@@ -301,6 +317,8 @@ __global__ __launch_bounds__(kEThreads) void jpeg_strip_kernel(
 // from zero; for x >= 0 that is trunc(x) + (x - trunc(x) >= 0.5), the
 // fraction exact in fp64.  A negative x clamps to 0 either way (trunc
 // toward zero gives <= 0 there), as does anything at or past 255.5.
+// Pinned by tests/test_gpu_jpeg_exact.py on samples an ulp either side of
+// k + 0.5 and past both clamps.
 __device__ __forceinline__ int round_clamp_u8(double x) {
   const int i = (int)x;                          // v_cvt_i32_f64: toward zero, saturating
   const int v = i + ((x - (double)i) >= 0.5 ? 1 : 0);

@@ -1203,7 +1203,10 @@ __device__ bool decode_stream_slow(const uint8_t *__restrict__ bits, uint32_t m,
   const int nbits = (int)(m & 0xFFFF), R = (int)((m >> 16) & 255), U = (int)(m >> 24);
   if (R == 0 || R > 2 * n) return false;
   const uint32_t *wds = reinterpret_cast<const uint32_t *>(bits);
-  int p = 0, got = 0, idx = 0, pending = -1;
+  // (a count may be any int16 of the table, negative ones included: whether a
+  // count is pending is a flag of its own, not a sign)
+  int p = 0, got = 0, idx = 0, pending = 0;
+  bool have = false;
   while (p < nbits) {
     const int wi = p >> 5, sh = p & 31;
     const uint32_t w0 = __builtin_bswap32(wds[wi]);
@@ -1221,11 +1224,12 @@ __device__ bool decode_stream_slow(const uint8_t *__restrict__ bits, uint32_t m,
     }
     if (hit < 0 || p + L > nbits) return false;
     const int v = (int16_t)(table[hit] & 0xFFFF);
-    if (pending < 0) {
+    if (!have) {
       pending = v;
+      have = true;
     } else {
       int cnt = pending;
-      pending = -1;
+      have = false;
       if (idx + cnt > n) cnt = n - idx;
       for (int j = 0; j < cnt; ++j) out[idx++] = (int16_t)v;
     }

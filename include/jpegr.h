@@ -140,6 +140,62 @@ int jpegr_entropy_decode_device(const void *d_bits, const void *d_meta,
                                 const void *d_table, size_t ntiles, void *d_coef,
                                 void *d_status, void *stream);
 
+/* The JPR stream: the entropy stage's output as one self-contained byte
+ * stream (this library defines it; all fields little-endian, no padding):
+ *   header   16 B   'J' 'P' 'R' '1' | u32 w | u32 h | u32 nimg
+ *   index    2 B x ntiles   u16 size of each tile record, raster order,
+ *                           images in sequence; ntiles = nimg * ceil(w/8) *
+ *                           ceil(h/8)
+ *   records  tile 0, tile 1, ...   each = stream(Y) stream(Cr) stream(Cb)
+ *   stream   u8 rle_len | u8 ncodes | u16 nbits   (the meta word's fields)
+ *            ncodes x { i16 value, u8 code_length }   the low 24 bits of
+ *                           d_table's words, in the table's (DFS) order
+ *            ceil(nbits / 8) bytes of bits, copied from the slot
+ * Only those bytes are copied: slot bytes past the final byte and table
+ * entries past ncodes do not reach the stream.  The slots bound a luma
+ * stream by ncodes <= 128, nbits <= 1024 (4 + 384 + 128 = 516 B) and a
+ * chroma stream by 64 and 512 (260 B): a tile record is at most 1,036 B.
+ * Stream length = 16 + 2 ntiles + the sum of the sizes; a record's offset is
+ * the exclusive scan of the index, so the stream decodes in parallel with no
+ * side input.
+ *
+ * jpegr_pack_bound: 16 + ntiles * (2 + 1036), 0 on bad dimensions.
+ * jpegr_pack_scratch_bytes: device scratch of either call below (16-B
+ * aligned).
+ * jpegr_pack_device: asynchronous on `stream`, no host read-back, nothing
+ * kept on the host between calls (capturable in a graph).  Stores a u64 at
+ * d_out_len (8-B aligned): the stream length, or the capacity needed when
+ * that exceeds `cap`, in which case nothing at or past d_out + cap is
+ * written.  d_out 16-B aligned; d_bits / d_meta / d_table as the entropy
+ * encoder leaves them.  A meta field past its slot is clamped to it.  Bad
+ * pointers or dimensions, or more than 2^32 tiles: JPEGR_ERR_ARG before any
+ * HIP call.
+ * jpegr_stream_info (host only): w, h, nimg of a header's 16 bytes;
+ * JPEGR_ERR_ARG on a wrong magic or a zero dimension.
+ * jpegr_unpack_device: the inverse, asynchronous on `stream`: every tile's
+ * meta word, its ncodes table entries and its bit bytes (whole dwords; the
+ * last one's spare bytes 0) back in the slot layout, for
+ * jpegr_entropy_decode_device as it is.  d_result: two u64 on the device,
+ *   [0] the length the header and index imply
+ *   [1] ~0 when the stream is consistent; 0 when the header or index is
+ *       wrong (magic, dimensions other than the arguments, in_len <
+ *       16 + 2 ntiles, implied length != in_len; every tile's meta is then
+ *       0); else 1 + t for the first tile t whose record is malformed (a
+ *       stream's rle_len, ncodes or nbits past its slot, or three streams
+ *       that do not sum to the indexed size); such a tile's meta words are 0
+ *       (ncodes = 0), the other tiles unpack.
+ * No read leaves [d_in, d_in + in_len) and every write stays inside its
+ * tile's slots, whatever the bytes say. */
+size_t jpegr_pack_bound(int w, int h, int nimg);
+size_t jpegr_pack_scratch_bytes(size_t ntiles);
+int jpegr_pack_device(const void *d_bits, const void *d_meta, const void *d_table,
+                      int w, int h, int nimg, void *d_out, size_t cap,
+                      void *d_out_len, void *d_scratch, void *stream);
+int jpegr_stream_info(const uint8_t header[16], int *w, int *h, int *nimg);
+int jpegr_unpack_device(const void *d_in, size_t in_len, int w, int h, int nimg,
+                        void *d_bits, void *d_meta, void *d_table,
+                        void *d_scratch, void *d_result, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

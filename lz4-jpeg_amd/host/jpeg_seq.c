@@ -14,6 +14,9 @@
  *          ../Output-Input/Images/coefficients.bin  the quantised zigzag
  *          coefficients: int16 LE per 8x8 tile [Y 64][Cr 32][Cb 32], tiles
  *          in raster order (the reference keeps them in memory only)
+ *          ../Output-Input/Images/coefficients.jpr  the same coefficients
+ *          entropy-coded: the JPR stream of jpegr.h (header, u16 size index,
+ *          per tile the Y, Cr, Cb streams' code tables and bits)
  *   exit 0; unreadable image: "Error loading image" and exit(1) (JPEG.c:74-78).
  * Colour planes, DCT, quantisation, zigzag, the entropy round trip the
  * reference runs per tile (RLE + Huffman encode, decode, inverse RLE,
@@ -64,7 +67,8 @@ int main(int argc, char **argv) {
   const size_t ntiles = ncoef / 128;
   void *d_rgba = NULL, *d_y = NULL, *d_cr = NULL, *d_cb = NULL, *d_coef = NULL, *d_rec = NULL;
   void *d_bits = NULL, *d_meta = NULL, *d_table = NULL, *d_scr = NULL, *d_st = NULL;
-  void *d_coef2 = NULL;
+  void *d_coef2 = NULL, *d_jpr = NULL, *d_jlen = NULL, *d_jscr = NULL;
+  const size_t jpr_cap = jpegr_pack_bound(w, h, 1);
   if (hipMalloc(&d_rgba, npx * 4) != hipSuccess || hipMalloc(&d_y, npx) != hipSuccess ||
       hipMalloc(&d_rec, npx * 4) != hipSuccess ||
       hipMalloc(&d_cr, npx) != hipSuccess || hipMalloc(&d_cb, npx) != hipSuccess ||
@@ -73,13 +77,17 @@ int main(int argc, char **argv) {
       hipMalloc(&d_meta, ntiles * 3 * 4) != hipSuccess ||
       hipMalloc(&d_table, ntiles * 256 * 4) != hipSuccess ||
       hipMalloc(&d_scr, jpegr_entropy_scratch_bytes(ntiles)) != hipSuccess ||
-      hipMalloc(&d_st, 16) != hipSuccess ||
+      hipMalloc(&d_st, 16) != hipSuccess || hipMalloc(&d_jpr, jpr_cap) != hipSuccess ||
+      hipMalloc(&d_jlen, 8) != hipSuccess ||
+      hipMalloc(&d_jscr, jpegr_pack_scratch_bytes(ntiles)) != hipSuccess ||
       hipMemset(d_st, 0, 16) != hipSuccess)
     fail("device allocation failed");
   if (hipMemcpy(d_rgba, rgba, npx * 4, hipMemcpyHostToDevice) != hipSuccess) fail("copy in");
   if (jpegr_planes_device(d_rgba, w, h, d_y, d_cr, d_cb, NULL) != JPEGR_OK ||
       jpegr_encode_device(d_rgba, w, h, 1, d_coef, NULL) != JPEGR_OK ||
       jpegr_entropy_encode_device(d_coef, ntiles, d_bits, d_meta, d_table, d_scr, d_st, NULL) !=
+          JPEGR_OK ||
+      jpegr_pack_device(d_bits, d_meta, d_table, w, h, 1, d_jpr, jpr_cap, d_jlen, d_jscr, NULL) !=
           JPEGR_OK ||
       jpegr_entropy_decode_device(d_bits, d_meta, d_table, ntiles, d_coef2, d_st, NULL) !=
           JPEGR_OK ||
@@ -88,15 +96,20 @@ int main(int argc, char **argv) {
   uint32_t st[2];
   if (hipMemcpy(st, d_st, 8, hipMemcpyDeviceToHost) != hipSuccess) fail("copy out");
   if (st[1] != 0) fail("entropy decode");
+  uint64_t jpr_len = 0;
+  if (hipMemcpy(&jpr_len, d_jlen, 8, hipMemcpyDeviceToHost) != hipSuccess) fail("copy out");
+  if (jpr_len > jpr_cap) fail("packed stream over its bound");
   uint8_t *y = malloc(npx), *cr = malloc(npx), *cb = malloc(npx), *vis = malloc(npx * 4);
   uint8_t *rec = malloc(npx * 4);
   int16_t *coef = malloc(ncoef * 2);
-  if (!y || !cr || !cb || !vis || !coef || !rec) fail("out of memory");
+  uint8_t *jpr = malloc(jpr_len);
+  if (!y || !cr || !cb || !vis || !coef || !rec || !jpr) fail("out of memory");
   if (hipMemcpy(y, d_y, npx, hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(cr, d_cr, npx, hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(cb, d_cb, npx, hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(coef, d_coef, ncoef * 2, hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(rec, d_rec, npx * 4, hipMemcpyDeviceToHost) != hipSuccess)
+      hipMemcpy(rec, d_rec, npx * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(jpr, d_jpr, jpr_len, hipMemcpyDeviceToHost) != hipSuccess)
     fail("copy out");
 
   write_png(out_dir, "original.png", w, h, rgba);                    /* JPEG.c:1105 */
@@ -126,9 +139,14 @@ int main(int argc, char **argv) {
   FILE *f = fopen(path, "wb");
   if (!f || fwrite(coef, 2, ncoef, f) != ncoef) fail("cannot write coefficients.bin");
   fclose(f);
+  snprintf(path, sizeof path, "%scoefficients.jpr", out_dir);
+  f = fopen(path, "wb");
+  if (!f || fwrite(jpr, 1, jpr_len, f) != jpr_len) fail("cannot write coefficients.jpr");
+  fclose(f);
+  (void)hipFree(d_jpr); (void)hipFree(d_jlen); (void)hipFree(d_jscr);
   (void)hipFree(d_rgba); (void)hipFree(d_y); (void)hipFree(d_cr); (void)hipFree(d_cb);
   (void)hipFree(d_coef); (void)hipFree(d_rec); (void)hipFree(d_coef2); (void)hipFree(d_bits);
   (void)hipFree(d_meta); (void)hipFree(d_table); (void)hipFree(d_scr); (void)hipFree(d_st);
-  free(rgba); free(y); free(cr); free(cb); free(vis); free(coef); free(rec);
+  free(rgba); free(y); free(cr); free(cb); free(vis); free(coef); free(rec); free(jpr);
   return 0;
 }

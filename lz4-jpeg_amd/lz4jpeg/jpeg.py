@@ -139,3 +139,124 @@ class Entropy:
         table = [(int((e & 0xFFFF) ^ 0x8000) - 0x8000, int((e >> 16) & 255)) for e in tab.tolist()]
         raw = self.bits[tile * 256 + off: tile * 256 + off + (nbits + 7) // 8].cpu().numpy()
         return {"rle_len": rle_len, "table": table, "nbits": nbits, "bits": raw.tobytes()}
+
+
+# ---- the JPR stream (include/jpegr.h): the entropy stage's output as bytes ------
+PACK_RECORD_MAX = 1036
+
+
+def pack_bound(w, h, nimg=1):
+    return int(_lib.lib().jpegr_pack_bound(w, h, nimg))
+
+
+def _pack_scratch(ntiles, device):
+    import torch
+    return torch.empty(int(_lib.lib().jpegr_pack_scratch_bytes(ntiles)), dtype=torch.uint8,
+                       device=device)
+
+
+def pack_device(ent, w, h, nimg=1, d_out=None, stream=None, d_len=None, scratch=None):
+    """Pack an Entropy's slots into one JPR stream.  Returns (d_out, d_len):
+    d_out a uint8 tensor (pack_bound bytes when not given), d_len a one-element
+    int64 tensor holding the stream length -- or the capacity needed when that
+    exceeds d_out's size, in which case nothing past d_out is written.
+    Asynchronous: no read-back."""
+    import torch
+    if nimg * tiles(w, h) != ent.ntiles:
+        raise ValueError("ent does not hold nimg * tiles(w, h) tiles")
+    dev = ent.bits.device
+    if d_out is None:
+        d_out = torch.empty(pack_bound(w, h, nimg), dtype=torch.uint8, device=dev)
+    if d_len is None:
+        d_len = torch.zeros(1, dtype=torch.int64, device=dev)
+    if scratch is None:
+        scratch = _pack_scratch(ent.ntiles, dev)
+    rc = _lib.lib().jpegr_pack_device(
+        ctypes.c_void_p(ent.bits.data_ptr()), ctypes.c_void_p(ent.meta.data_ptr()),
+        ctypes.c_void_p(ent.table.data_ptr()), w, h, nimg, ctypes.c_void_p(d_out.data_ptr()),
+        d_out.numel(), ctypes.c_void_p(d_len.data_ptr()), ctypes.c_void_p(scratch.data_ptr()),
+        _stream_handle(stream))
+    if rc != 0:
+        raise JpegError(rc, "jpegr_pack_device")
+    return d_out, d_len
+
+
+def unpack_device(d_stream, in_len, w, h, nimg=1, ent=None, stream=None, d_result=None,
+                  scratch=None):
+    """A JPR stream's first in_len bytes back into an Entropy's slots.  Returns
+    (Entropy, d_result): d_result two int64 on the device, [0] the length the
+    header and index imply, [1] -1 (all ones) when the stream is consistent, 0
+    when its header or index is wrong, 1 + t for the first malformed tile t
+    (jpegr.h).  Asynchronous: no read-back."""
+    import torch
+    nt = nimg * tiles(w, h)
+    if ent is None:
+        ent = Entropy(nt, device=d_stream.device)
+    elif ent.ntiles != nt:
+        raise ValueError("ent does not hold nimg * tiles(w, h) tiles")
+    if in_len > d_stream.numel():
+        raise ValueError("in_len past the end of d_stream")
+    if d_result is None:
+        d_result = torch.zeros(2, dtype=torch.int64, device=d_stream.device)
+    if scratch is None:
+        scratch = _pack_scratch(nt, d_stream.device)
+    rc = _lib.lib().jpegr_unpack_device(
+        ctypes.c_void_p(d_stream.data_ptr()), in_len, w, h, nimg,
+        ctypes.c_void_p(ent.bits.data_ptr()), ctypes.c_void_p(ent.meta.data_ptr()),
+        ctypes.c_void_p(ent.table.data_ptr()), ctypes.c_void_p(scratch.data_ptr()),
+        ctypes.c_void_p(d_result.data_ptr()), _stream_handle(stream))
+    if rc != 0:
+        raise JpegError(rc, "jpegr_unpack_device")
+    return ent, d_result
+
+
+def stream_info(header_bytes):
+    """(w, h, nimg) of a JPR stream's first 16 bytes; JpegError on a wrong
+    magic or a zero dimension."""
+    hdr = bytes(header_bytes[:16])
+    if len(hdr) < 16:
+        raise ValueError("a JPR header is 16 bytes")
+    w, h, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    rc = _lib.lib().jpegr_stream_info(ctypes.c_char_p(hdr), ctypes.byref(w), ctypes.byref(h),
+                                      ctypes.byref(n))
+    if rc != 0:
+        raise JpegError(rc, "jpegr_stream_info")
+    return w.value, h.value, n.value
+
+
+def compress_device(d_rgba, w, h, nimg=1):
+    """RGBA8 images -> a uint8 tensor of exactly the JPR stream: encode,
+    entropy encode, pack; the length is read back once, then the encoder's
+    status word.  Raises JpegError if a stream overflowed the reference's
+    buffers (status[0] != 0)."""
+    d_coef = encode_device(d_rgba, w, h, nimg)
+    ent = Entropy(nimg * tiles(w, h), device=d_rgba.device)
+    ent.encode(d_coef)
+    d_out, d_len = pack_device(ent, w, h, nimg)
+    n = int(d_len.item())
+    if int(ent.status[0].item()) != 0:
+        raise JpegError(-1, "compress_device: a stream overflows the reference's buffers")
+    return d_out[:n].clone()
+
+
+def decompress_device(d_stream):
+    """A JPR stream (uint8 tensor, exactly the stream) -> (rgba uint8 tensor,
+    w, h, nimg): reads the 16 header bytes back, then unpack, entropy decode
+    and reconstruct.  No d_orig is passed to the reconstruction, so every tile
+    is decoded (the reference leaves its trailing tiles untransformed; see
+    jpegr_reconstruct_device).  Raises JpegError on an inconsistent stream
+    (d_result[1] != ~0) or a malformed entropy stream (status[1] != 0)."""
+    import torch
+    if d_stream.numel() < 16:
+        raise JpegError(-1, "decompress_device: shorter than a header")
+    w, h, nimg = stream_info(d_stream[:16].cpu().numpy().tobytes())
+    ent, d_result = unpack_device(d_stream, d_stream.numel(), w, h, nimg)
+    d_coef = torch.empty(nimg * coef_count(w, h), dtype=torch.int16, device=d_stream.device)
+    ent.decode(d_coef)
+    out = reconstruct_device(d_coef, w, h, nimg)
+    if int(d_result[1].item()) != -1:
+        raise JpegError(-1, f"decompress_device: inconsistent stream (verdict "
+                            f"{int(d_result[1].item())})")
+    if int(ent.status[1].item()) != 0:
+        raise JpegError(-1, "decompress_device: malformed entropy stream")
+    return out, w, h, nimg

@@ -1,0 +1,139 @@
+#!/usr/bin/env python3
+"""Time the JPR stream stage (jpegr_pack_device / jpegr_unpack_device) and
+jpeg.compress_device on an MI355X; bench.py's discipline: a clock pre-warm,
+settle() on each measured call, then event-timed means over back-to-back
+launches.
+
+    python tools/jpeg_pack_bench.py [--steps K] [--once N]
+
+Images: bench.py's 3840x2160 random image (synth.rand_rgba_device, seed 1)
+and a 3840x2160 smooth one (tests/test_gpu_entropy.py's generator).  Prints
+one JSON line per image: ms per image of pack and unpack (beside the entropy
+stage's encode / decode, measured in the same run), the stream's bytes per
+tile and its ratio to the tile's 256 B of RGBA, and the algorithmic bytes of
+each call (live slot bytes read + stream bytes written, and the reverse) with
+the rate they imply.  --once N: N pack + unpack launches per image and
+nothing else, for a profiler's counter passes."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "lz4-jpeg_amd"))
+
+W, H = 3840, 2160
+
+
+def settle(fn, sync, ms=60.0, chunk=8):
+    t0, n = time.perf_counter(), 0
+    while time.perf_counter() - t0 < ms / 1e3:
+        for _ in range(chunk):
+            fn()
+        n += chunk
+        sync()
+    return n
+
+
+def smooth_image(w, h):
+    yy, xx = np.mgrid[0:h, 0:w]
+    return np.ascontiguousarray(np.stack([(xx // 3) % 256, (yy // 2) % 256, ((xx + yy) // 5) % 256,
+                                          np.full_like(xx, 255)], -1).astype(np.uint8))
+
+
+def timed(fn, steps, torch):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(steps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / steps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--once", type=int, default=0)
+    args = ap.parse_args()
+    import torch
+    from lz4jpeg import jpeg, synth
+    if not torch.cuda.is_available():
+        sys.exit("jpeg_pack_bench: needs a GPU (there is no CPU path to time)")
+    dev = torch.device("cuda:0")
+    nt = jpeg.tiles(W, H)
+    images = {}
+    d_img = torch.empty(W * H * 4, dtype=torch.uint8, device=dev)
+    synth.rand_rgba_device(d_img, 0, W * H, seed=1)
+    images["random"] = d_img
+    images["smooth"] = torch.from_numpy(smooth_image(W, H)).to(dev).reshape(-1)
+
+    if not args.once:                       # clock pre-warm (bench.py run_lz4)
+        d_warm = torch.zeros(256 << 20, dtype=torch.uint8, device=dev)
+        settle(lambda: d_warm.add_(1), torch.cuda.synchronize, ms=100.0, chunk=16)
+        del d_warm
+
+    for name, img in images.items():
+        d_coef = jpeg.encode_device(img, W, H)
+        ent = jpeg.Entropy(nt, device=dev)
+        ent.encode(d_coef)
+        back = jpeg.Entropy(nt, device=dev)
+        d_out = torch.empty(jpeg.pack_bound(W, H), dtype=torch.uint8, device=dev)
+        d_len = torch.zeros(1, dtype=torch.int64, device=dev)
+        d_res = torch.zeros(2, dtype=torch.int64, device=dev)
+        s1 = torch.empty(int(jpeg._lib.lib().jpegr_pack_scratch_bytes(nt)), dtype=torch.uint8, device=dev)
+        s2 = torch.empty_like(s1)
+        jpeg.pack_device(ent, W, H, d_out=d_out, d_len=d_len, scratch=s1)
+        n = int(d_len.item())
+
+        def pack():
+            jpeg.pack_device(ent, W, H, d_out=d_out, d_len=d_len, scratch=s1)
+
+        def unpack():
+            jpeg.unpack_device(d_out, n, W, H, ent=back, d_result=d_res, scratch=s2)
+
+        if args.once:
+            for _ in range(args.once):
+                pack()
+                unpack()
+            torch.cuda.synchronize()
+            continue
+        unpack()
+        d_coef2 = torch.empty_like(d_coef)
+        back.decode(d_coef2)
+        torch.cuda.synchronize()
+        ok = d_res.cpu().tolist() == [n, -1] and bool(torch.equal(d_coef2, d_coef)) \
+            and int(back.status[1].item()) == 0
+        meta = ent.meta.to(torch.int64) & 0xFFFFFFFF
+        live = 12 * nt + 4 * int((meta >> 24).sum().item()) + \
+            int((((meta & 0xFFFF) + 7) // 8).sum().item())          # slot bytes that matter
+        res = {"image": f"{name} {W}x{H}", "tiles": nt, "stream_bytes": n,
+               "bytes_per_tile": round(n / nt, 2), "ratio_to_rgba": round(n / (256 * nt), 4),
+               "roundtrip_ok": ok, "steps": args.steps}
+        for key, fn in (("pack", pack), ("unpack", unpack), ("entropy_encode", lambda: ent.encode(d_coef)),
+                        ("entropy_decode", lambda: back.decode(d_coef2))):
+            warm = settle(fn, torch.cuda.synchronize, chunk=20)
+            res[key + "_ms"] = round(timed(fn, args.steps, torch), 4)
+            res[key + "_warmup"] = warm
+        # pack reads the live slot bytes and writes the stream (its index twice:
+        # u32 for the scan, u16 in the stream); unpack the reverse
+        alg = live + n + 2 * 4 * nt
+        res["algorithmic_bytes"] = alg
+        res["pack_alg_gbs"] = round(alg / (res["pack_ms"] / 1e3) / 1e9, 1)
+        res["unpack_alg_gbs"] = round(alg / (res["unpack_ms"] / 1e3) / 1e9, 1)
+        settle(lambda: jpeg.compress_device(img, W, H), torch.cuda.synchronize, chunk=4)
+        t0 = time.perf_counter()
+        k = max(1, args.steps // 10)
+        for _ in range(k):
+            jpeg.compress_device(img, W, H)
+        torch.cuda.synchronize()
+        res["compress_device_ms"] = round((time.perf_counter() - t0) / k * 1e3, 4)
+        res["compress_device_note"] = "host clock; allocates its buffers and reads the length back"
+        print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()

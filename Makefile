@@ -4,6 +4,7 @@
 #   lz4-jpeg_amd/lz4jpeg/liblz4jpeg.so   product C-ABI library (HIP kernels)
 #   lz4-jpeg_amd/bin/LZ4_seq, JPEG_seq    drop-in executables (file contract),
 #                                         also as LZ4_seq.exe / JPEG_seq.exe
+#   lz4-jpeg_amd/bin/JPEG_dec             coefficients.jpr -> PNG (also JPEG_dec.exe)
 #   oracle/liboracle.so (+ oracle/_ref)   test-only CPU checker
 HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
@@ -28,9 +29,9 @@ HDRS    := include/lz4r.h include/jpegr.h include/lz4jpeg_compat.h include/lz4jp
            $(CSRC)/wave64.h $(CSRC)/lz4r_prof.h $(CSRC)/lz4r_layout.h $(CSRC)/lz4r_tile_lds.h \
            $(CSRC)/lz4r_tiles.h $(CSRC)/lz4r_matches.h $(CSRC)/lz4r_scan.h $(CSRC)/lz4r_emit.h \
            $(CSRC)/lz4r_dec_layout.h $(CSRC)/lz4r_dec_parse.h $(CSRC)/lz4r_dec_blocks.h \
-           $(CSRC)/lz4r_dec_bare.h
+           $(CSRC)/lz4r_dec_bare.h $(CSRC)/jpegr_pack_common.h
 OBJS    := $(B)/lz4r.o $(B)/lz4r_gpudec.o $(B)/jpegr.o $(B)/jpegr_blocks.o $(B)/jpegr_entropy.o \
-           $(B)/jpegr_pack.o \
+           $(B)/jpegr_pack.o $(B)/jpegr_stream.o \
            $(B)/synth.o $(B)/synth_dev.o \
            $(B)/lz4r_decode.o $(B)/compat.o $(B)/compat_lz4.o
 
@@ -39,7 +40,8 @@ all: lib bin oracle tools
 lib: $(LIB)
 
 bin: $(BIN)/LZ4_seq $(BIN)/JPEG_seq $(BIN)/LZ4_seq.exe $(BIN)/JPEG_seq.exe \
-     $(BIN)/LZ4_par $(BIN)/JPEG_par $(BIN)/LZ4_par.exe $(BIN)/JPEG_par.exe
+     $(BIN)/LZ4_par $(BIN)/JPEG_par $(BIN)/LZ4_par.exe $(BIN)/JPEG_par.exe \
+     $(BIN)/JPEG_dec $(BIN)/JPEG_dec.exe
 
 $(CSRC)/jpeg_tables.h: $(CSRC)/gen_jpeg_tables.py
 	python3 $< > $@
@@ -64,6 +66,10 @@ $(BIN)/LZ4_seq: $(B)/lz4_seq.o $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -o $@ $^
 
 $(BIN)/JPEG_seq: $(B)/jpeg_seq.o $(B)/png_io.o $(OBJS)
+	@mkdir -p $(BIN)
+	$(HIPCC) --offload-arch=$(ARCH) -o $@ $^ -lz
+
+$(BIN)/JPEG_dec: $(B)/jpeg_dec.o $(B)/png_io.o $(OBJS)
 	@mkdir -p $(BIN)
 	$(HIPCC) --offload-arch=$(ARCH) -o $@ $^ -lz
 

@@ -196,6 +196,42 @@ int jpegr_unpack_device(const void *d_in, size_t in_len, int w, int h, int nimg,
                         void *d_bits, void *d_meta, void *d_table,
                         void *d_scratch, void *d_result, void *stream);
 
+/* Entropy decode straight from a JPR stream, whole or by tile range: tiles
+ * [tile0, tile0 + ntile) of the stream in d_in[0, in_len) -- numbered in
+ * raster order through all images, as the index numbers them; image i of a
+ * stream is the range [i * tiles, (i + 1) * tiles) -- to ntile * 128 int16 at
+ * d_coef in jpegr_encode_device's layout, tile tile0 + i at d_coef + 128 i.
+ * No slots are allocated, written or read.  Asynchronous on `stream`, no host
+ * read-back, nothing kept on the host between calls.
+ * d_scratch: jpegr_pack_scratch_bytes(tiles of the whole stream) bytes, 16-B
+ * aligned (the index scan is pack's and unpack's).  d_coef 16-B aligned; d_in
+ * as for jpegr_unpack_device (any alignment).  NULL pointers, bad dimensions,
+ * ntile == 0, tile0 + ntile past the stream's tile count, more than 2^32
+ * tiles, a misaligned d_coef, d_scratch or d_result: JPEGR_ERR_ARG before any
+ * HIP call.
+ * d_result: three u64 on the device (8-B aligned), initialised by the call's
+ * own first launch -- no memset before it, no tag, no spin: the call can be
+ * captured in a graph and replayed, and several calls may be in flight at
+ * once, each with its own d_result and d_scratch.
+ *   [0] the length the header and index imply (as jpegr_unpack_device)
+ *   [1] ~0 when consistent; 0 when the header or index is wrong (unpack's
+ *       conditions, against the w, h, nimg arguments; every selected tile's
+ *       128 ints are then 0); else 1 + t for the first tile t in
+ *       [tile0, tile0 + ntile) whose record is malformed (unpack's record
+ *       rules; t counts from the stream's first tile).  A malformed record's
+ *       128 ints are 0; records outside the range are not examined.
+ *   [2] the streams inside the range, in well-formed records, that the
+ *       entropy decoder rejects (what jpegr_entropy_decode_device counts in
+ *       d_status[1]): this call's count, never accumulated.  A rejected
+ *       stream's 64 or 32 ints are 0; every other stream decodes exactly.
+ * Whatever the bytes say, no read leaves [d_in, d_in + in_len) and no write
+ * leaves [d_coef, d_coef + 256 ntile) and the scratch: table entries and bit
+ * bytes are read at byte granularity inside their own checked record, never
+ * as chunks that reach into the next record or past the end. */
+int jpegr_stream_decode_device(const void *d_in, size_t in_len, int w, int h, int nimg,
+                               size_t tile0, size_t ntile, void *d_coef,
+                               void *d_scratch, void *d_result, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -224,6 +224,68 @@ def stream_info(header_bytes):
     return w.value, h.value, n.value
 
 
+def decode_stream_device(d_stream, in_len, w, h, nimg=1, tile0=0, ntiles=None, d_coef=None,
+                         d_result=None, scratch=None, stream=None):
+    """Tiles [tile0, tile0 + ntiles) of a JPR stream's first in_len bytes
+    straight to coefficients (jpegr_stream_decode_device: no slots; ntiles
+    None = up to the stream's last tile).  Returns (d_coef, d_result): d_coef
+    int16, 128 per selected tile; d_result three int64 on the device, [0] the
+    length the header and index imply, [1] -1 (all ones) when consistent, 0 on
+    a wrong header or index, 1 + t for the first malformed tile t of the
+    range, [2] the range's rejected entropy streams (jpegr.h).  Asynchronous:
+    no read-back."""
+    import torch
+    nt = nimg * tiles(w, h)
+    if ntiles is None:
+        ntiles = nt - tile0
+    if in_len > d_stream.numel():
+        raise ValueError("in_len past the end of d_stream")
+    if tile0 < 0 or ntiles <= 0 or tile0 + ntiles > nt:
+        raise ValueError("tile range outside the stream")
+    if d_coef is None:
+        d_coef = torch.empty(ntiles * 128, dtype=torch.int16, device=d_stream.device)
+    elif d_coef.numel() * d_coef.element_size() < ntiles * 256:
+        raise ValueError("d_coef smaller than ntiles * 128 int16")
+    if d_result is None:
+        d_result = torch.empty(3, dtype=torch.int64, device=d_stream.device)
+    if scratch is None:
+        scratch = _pack_scratch(nt, d_stream.device)
+    rc = _lib.lib().jpegr_stream_decode_device(
+        ctypes.c_void_p(d_stream.data_ptr()), in_len, w, h, nimg, tile0, ntiles,
+        ctypes.c_void_p(d_coef.data_ptr()), ctypes.c_void_p(scratch.data_ptr()),
+        ctypes.c_void_p(d_result.data_ptr()), _stream_handle(stream))
+    if rc != 0:
+        raise JpegError(rc, "jpegr_stream_decode_device")
+    return d_coef, d_result
+
+
+def decompress_images_device(d_stream, first=0, count=None):
+    """Images [first, first + count) of a JPR stream (uint8 tensor, exactly
+    the stream; count None = up to the last) -> (rgba uint8 tensor, w, h,
+    count): reads the 16 header bytes back, decodes the images' tile range
+    straight from the stream and reconstructs it (every tile decoded, as
+    decompress_device).  The other images are not touched.  Raises JpegError
+    on an inconsistent stream (d_result[1] != ~0) or a rejected entropy stream
+    (d_result[2] != 0)."""
+    if d_stream.numel() < 16:
+        raise JpegError(-1, "decompress_images_device: shorter than a header")
+    w, h, nimg = stream_info(d_stream[:16].cpu().numpy().tobytes())
+    if count is None:
+        count = nimg - first
+    if first < 0 or count <= 0 or first + count > nimg:
+        raise ValueError("image range outside the stream")
+    per = tiles(w, h)
+    d_coef, d_result = decode_stream_device(d_stream, d_stream.numel(), w, h, nimg, first * per,
+                                            count * per)
+    out = reconstruct_device(d_coef, w, h, count)
+    res = d_result.cpu().tolist()
+    if res[1] != -1:
+        raise JpegError(-1, f"decompress_images_device: inconsistent stream (verdict {res[1]})")
+    if res[2] != 0:
+        raise JpegError(-1, "decompress_images_device: malformed entropy stream")
+    return out, w, h, count
+
+
 def compress_device(d_rgba, w, h, nimg=1):
     """RGBA8 images -> a uint8 tensor of exactly the JPR stream: encode,
     entropy encode, pack; the length is read back once, then the encoder's

@@ -13,7 +13,17 @@ stage's encode / decode, measured in the same run), the stream's bytes per
 tile and its ratio to the tile's 256 B of RGBA, and the algorithmic bytes of
 each call (live slot bytes read + stream bytes written, and the reverse) with
 the rate they imply.  --once N: N pack + unpack launches per image and
-nothing else, for a profiler's counter passes."""
+nothing else, for a profiler's counter passes.
+
+--decode: the decode side only, for profiles/jpr_stream_decode.log: the direct
+decode of the stream (jpegr_stream_decode_device) against the two stages it
+replaces, unpack + entropy decode, all in this run after the same pre-warm
+and settle, alternated over --rounds rounds so that the spread between
+repeats of the same call is known before a difference is read; then one image
+of an 8-image stream (the random image eight times) against the two stages
+over the whole of that stream, which is the only way to that image without
+the direct decode; and the device bytes a 4K decode needs either way.  With
+--once N: N direct decodes per image and nothing else."""
 import argparse
 import json
 import os
@@ -54,10 +64,113 @@ def timed(fn, steps, torch):
     return e0.elapsed_time(e1) / steps
 
 
+def spread(xs):
+    xs = sorted(xs)
+    return {"min": round(xs[0], 4), "median": round(xs[len(xs) // 2], 4), "max": round(xs[-1], 4)}
+
+
+def decode_side(args, torch, jpeg, name, img, d_coef, d_out, n, back, d_res, s2, unpack):
+    """The direct decode beside unpack + entropy decode: same run, alternated."""
+    dev = d_coef.device
+    nt = jpeg.tiles(W, H)
+    lib = jpeg._lib.lib()
+    pack_scratch = int(lib.jpegr_pack_scratch_bytes(nt))
+    d_direct = torch.empty_like(d_coef)
+    d_res3 = torch.empty(3, dtype=torch.int64, device=dev)
+    s3 = torch.empty(pack_scratch, dtype=torch.uint8, device=dev)
+    d_coef2 = torch.empty_like(d_coef)
+
+    def direct():
+        jpeg.decode_stream_device(d_out, n, W, H, d_coef=d_direct, d_result=d_res3, scratch=s3)
+
+    def entropy_decode():
+        back.decode(d_coef2)
+
+    def two_stages():
+        unpack()
+        entropy_decode()
+
+    if args.once:
+        for _ in range(args.once):
+            direct()
+        torch.cuda.synchronize()
+        return
+    two_stages()
+    direct()
+    torch.cuda.synchronize()
+    ok = d_res.cpu().tolist() == [n, -1] and int(back.status[1].item()) == 0 \
+        and bool(torch.equal(d_coef2, d_coef)) and d_res3.cpu().tolist() == [n, -1, 0] \
+        and bool(torch.equal(d_direct, d_coef))
+    res = {"image": f"{name} {W}x{H}", "tiles": nt, "stream_bytes": n, "outputs_equal": ok,
+           "steps": args.steps, "rounds": args.rounds}
+    calls = (("unpack", unpack), ("entropy_decode", entropy_decode), ("two_stages", two_stages),
+             ("stream_decode", direct))
+    ms = {k: [] for k, _ in calls}
+    for _ in range(args.rounds):                     # alternated: each round times every call once
+        for key, fn in calls:
+            settle(fn, torch.cuda.synchronize, chunk=20)
+            ms[key].append(timed(fn, args.steps, torch))
+    for key, _ in calls:
+        res[key + "_ms"] = spread(ms[key])
+    res["stream_decode_over_two_stages"] = round(
+        res["stream_decode_ms"]["median"] / res["two_stages_ms"]["median"], 3)
+    # device memory a decode of this image needs beside the stream and the
+    # coefficients: the slots, the decoder's status and unpack's result and
+    # scratch -- or the direct decode's result and scratch
+    common = n + 256 * nt
+    res["device_bytes_two_stages"] = common + 1292 * nt + 16 + 16 + pack_scratch
+    res["device_bytes_stream_decode"] = common + 24 + pack_scratch
+    print(json.dumps(res), flush=True)
+    if name != "random":
+        return
+    # one image of an 8-image stream
+    k, pick = 8, 5
+    img8 = img.repeat(k)
+    ent8 = jpeg.Entropy(k * nt, device=dev)
+    ent8.encode(jpeg.encode_device(img8, W, H, k))
+    d_out8, d_len8 = jpeg.pack_device(ent8, W, H, k)
+    n8 = int(d_len8.item())
+    del img8
+    res8 = torch.empty(3, dtype=torch.int64, device=dev)
+    res8u = torch.zeros(2, dtype=torch.int64, device=dev)
+    s8 = torch.empty(int(lib.jpegr_pack_scratch_bytes(k * nt)), dtype=torch.uint8, device=dev)
+    s8u = torch.empty_like(s8)
+    d_all = torch.empty(k * nt * 128, dtype=torch.int16, device=dev)
+
+    def one_image():
+        jpeg.decode_stream_device(d_out8, n8, W, H, k, pick * nt, nt, d_coef=d_direct, d_result=res8,
+                                  scratch=s8)
+
+    def all_direct():
+        jpeg.decode_stream_device(d_out8, n8, W, H, k, d_coef=d_all, d_result=res8, scratch=s8)
+
+    def all_two_stages():
+        jpeg.unpack_device(d_out8, n8, W, H, k, ent=ent8, d_result=res8u, scratch=s8u)
+        ent8.decode(d_all)
+
+    one_image()
+    torch.cuda.synchronize()
+    ok8 = res8.cpu().tolist() == [n8, -1, 0] and bool(torch.equal(d_direct, d_coef))
+    out = {"image": f"random {W}x{H} x {k}", "tiles": k * nt, "stream_bytes": n8, "image_decoded": pick,
+           "outputs_equal": ok8, "steps": args.steps, "rounds": args.rounds}
+    calls = (("one_image_stream_decode", one_image), ("all_images_stream_decode", all_direct),
+             ("all_images_two_stages", all_two_stages))
+    ms = {key: [] for key, _ in calls}
+    for _ in range(args.rounds):
+        for key, fn in calls:
+            settle(fn, torch.cuda.synchronize, chunk=4)
+            ms[key].append(timed(fn, max(1, args.steps // 4), torch))
+    for key, _ in calls:
+        out[key + "_ms"] = spread(ms[key])
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--once", type=int, default=0)
+    ap.add_argument("--decode", action="store_true")
+    ap.add_argument("--rounds", type=int, default=5)
     args = ap.parse_args()
     import torch
     from lz4jpeg import jpeg, synth
@@ -95,6 +208,9 @@ def main():
         def unpack():
             jpeg.unpack_device(d_out, n, W, H, ent=back, d_result=d_res, scratch=s2)
 
+        if args.decode:
+            decode_side(args, torch, jpeg, name, img, d_coef, d_out, n, back, d_res, s2, unpack)
+            continue
         if args.once:
             for _ in range(args.once):
                 pack()

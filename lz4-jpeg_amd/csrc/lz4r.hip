@@ -11,7 +11,7 @@
 //
 //   lz4r_layout.h    what the kernels and run() share: the block grid, the
 //                    record scratch, the scan's grouping, the error bit
-//   lz4r_tiles.h     lz4_tiles: one wave per block, match finder and greedy
+//   lz4r_tiles.h     lz4_tiles: one wave per run of blocks, match finder and greedy
 //                    parse -> sequence records and the block's byte count
 //                    (its LDS layout and primitives: lz4r_tile_lds.h)
 //   lz4r_matches.h   lz4_matches, lz4_window_matches: the batch match finders
@@ -46,7 +46,8 @@
 #include "lz4r_scan.h"
 #include "lz4r_emit.h"
 
-// Launch chunking: lz4_tiles is a 64-lane workgroup per block, and a HIP
+// Launch chunking: lz4_tiles was a 64-lane workgroup per block (now per run
+// of kTileRun blocks; the chunk size stayed), and a HIP
 // grid may not exceed 2^32 work-items, so a call is cut into chunks of at
 // most kChunk blocks (5.03 GB of input; a multiple of the scan partial, so
 // every chunk starts on a gather group and a partial).  The block slots are
@@ -216,15 +217,17 @@ int run(lz4r_ctx *c, const void *d_in, size_t n, void *d_out, size_t cap,
     const size_t nbc = std::min(kChunk, nb - b0);
     const size_t b1 = b0 + nbc;
     const uint32_t last_n = (uint32_t)(b1 == nb ? n - (nb - 1) * kBlk : kBlk);
-    // one block per workgroup: the hardware dispatcher balances the uneven
-    // per-block cost (a static grid-stride split leaves a tail; measured
-    // slower also with the next block prefetched into registers)
-    const uint32_t per = (uint32_t)((nbc + 7) / 8);    // blocks per XCD slice
+    // a run of kTileRun consecutive blocks per workgroup (lz4r_tiles.h); the
+    // hardware dispatcher balances the runs' uneven cost (a static
+    // grid-stride split of the whole launch leaves a tail)
+    // runs, then blocks, per XCD slice
+    const uint32_t runs = (uint32_t)((nbc + 8 * kTileRun - 1) / (8 * kTileRun));
+    const uint32_t per = runs * kTileRun;
     hipEvent_t t0 = timed ? (k == 0 ? ts->a : ts->tiles[2 * k]) : nullptr;   // chunk 0 starts the call
     hipEvent_t t1 = timed ? ts->tiles[2 * k + 1] : nullptr;
     // (every chunk starts 300 b0 bytes in: a multiple of 4)
     const auto tiles = ((uintptr_t)in & 3) == 0 ? lz4_tiles<true> : lz4_tiles<false>;
-    hipExtLaunchKernelGGL(tiles, dim3(8 * per), dim3(64), 0, s, t0, t1, 0u, in + b0 * kBlk,
+    hipExtLaunchKernelGGL(tiles, dim3(8 * runs), dim3(64), 0, s, t0, t1, 0u, in + b0 * kBlk,
                           (uint32_t)nbc, per, last_n, c->slots, ovfs, c->tsz + b0,
                           c->bsizes + b0, c->status);
     const size_t p0 = b0 / kPart, np = (nbc + kPart - 1) / kPart;

@@ -18,6 +18,15 @@ namespace {
 constexpr int kBlk = LZ4R_BLOCK;          // 300
 constexpr int kBlkOutMax = 560;           // >= 548: worst-case bytes of one block, 16-B multiple
 
+// lz4_tiles: consecutive blocks one wave (= one workgroup) encodes, one after
+// the other (a static run; DESIGN 8 has the A/B over 1, 2, 4, 8, 16).  The
+// host rounds an XCD's slice of the launch up to whole runs.
+#ifndef LZ4R_RUN
+#define LZ4R_RUN 16
+#endif
+constexpr int kTileRun = LZ4R_RUN;
+static_assert(kTileRun >= 1 && kTileRun <= 64, "blocks per lz4_tiles workgroup");
+
 // The first kHeadW dwords (header + 23 records: all of a text block's but for
 // ~7 % of blocks) go to a dense head array, kHead bytes per block, so lz4_emit
 // reads its 32 blocks' heads as one contiguous 3 KB run of 16-B loads (no

@@ -19,7 +19,10 @@ __global__ __launch_bounds__(64) void lz4_matches(const uint8_t *__restrict__ in
   for (int i = lane; i < n; i += 64) S.buf[kInOff + i] = src[i];
   if (lane < 16) S.buf[kInOff + n + lane] = 0;
   wave_sync();
-  encode_block<true, false>(S, n, nullptr, mout + (size_t)t * kBlk, nullptr, nullptr, nullptr);
+  TileKeys K;                            // (unused: the block is staged)
+  ProfClock prof = PROF_START();
+  encode_block<true, false>(S, n, nullptr, K, nullptr, mout + (size_t)t * kBlk, nullptr, nullptr,
+                            nullptr, lane, prof);
 }
 
 // find_longest_match over a block of any length n (block_encode with a

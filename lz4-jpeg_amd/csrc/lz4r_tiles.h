@@ -1,10 +1,44 @@
 // lz4r_tiles.h -- lz4_tiles, the compressor's compute kernel, and the batch
 // match finders that share its index.
 //
-// lz4_tiles: workgroup = one wave = one 300-B block (4,976 B of LDS, <= 64
-// VGPRs -> 8 waves per SIMD; occupancy is what this LDS- and issue-bound
-// kernel lives on).  Per block:
-//   stage    the block's 75 dwords -> LDS (the only read of the input).
+// lz4_tiles: workgroup = one wave = a run of kTileRun consecutive 300-B blocks,
+// encoded one after the other (4,976 B of LDS, <= 64 VGPRs -> 8 waves per
+// SIMD; occupancy is what this LDS- and issue-bound kernel lives on).  A
+// one-block wave spent its first stretch waiting for its block's bytes from
+// HBM while holding one of its SIMD's 8 slots; in a run only the first block
+// does, every other finds its dwords in registers, loaded while the block
+// before was encoded.
+//
+// Reuse of the LDS by the next block of a run needs no clean-up, by the same
+// argument that lets a fresh workgroup start on whatever the last one left
+// there -- every array is written by a block before that block reads it, and
+// the wave's LDS operations are served in program order:
+//   heads     a block reads only heads its own positions hash to, and each
+//             position empties its head before the first exchange (xchg_rtn5);
+//             the dummy slots rec[192 + lane] that inactive positions
+//             exchange with are emptied first in the same way
+//   ent, rec  ent[p] stored for every position a chain can reach and rec[]
+//             zeroed whole (ent_store_rec_zero_addtid) after the heads' last
+//             exchange, before the walk reads either
+//   queue     entries [0, qn) written, then exactly those read (reads past qn
+//             are masked off by idx4 < qwr4)
+//   cand      [0, ncand) written by the passes, then exactly those drained
+//   keys      all 320 stored (keys_store_addtid) before a drain reads them
+//   word      all 320 stored by the word pass before the walk; seq [0, Sv)
+//             written by the redone walk before the records read it
+//   staged    a staged block writes its n bytes and 16 zero bytes of pad
+//             first; byte kInOff - 1 (blk[-1]) is any byte: position 0 is
+//             left-maximal by its own bit
+// and the registers a block starts from (lane, the kernel arguments, m0 and
+// the priority, both set by the asm blocks that use them) do not depend on
+// the block before.  tests/test_gpu_lz4_runs.py pins it against the oracle.
+//
+// Per block:
+//   load     a lane's five positions need 14 dwords (TileKeys), straight from
+//            global memory into registers -- the only read of the input; the
+//            block is NOT staged in LDS, except the launch's last block, the
+//            one before a last block of < 24 bytes and unaligned inputs
+//            (bytewise, with a zero pad).
 //   position-major (lane l owns p = 64 r + l, r = 0..4):
 //     index  per-bucket chains of the 4-gram starts by a 10-bit hash: each
 //            position empties its bucket's u32 head, then exchanges itself
@@ -49,26 +83,79 @@
 
 namespace {
 
-// Encode the staged block (n bytes at S.buf[kInOff]) as sequence records:
+// The dwords of a kFull block that lane l's five positions 64 r + l need,
+// straight from global memory (src 4-byte aligned; d = l >> 2): dwords d and
+// d + 1 for row 0 (one global_load_dwordx2), dwords 16 r + d - 1 .. + 1 for
+// rows 1..4 (the dword before carries blk[p - 1]; one global_load_dwordx3
+// each).  Row 4's lanes read up to 24 bytes past the block's 300.
+// Held as the loads' own register tuples: carried around lz4_tiles' loop as
+// single dwords, each load's result was copied out of its tuple -- and
+// waited for -- right after the load was issued.
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
+struct TileKeys {
+  u32x2 r0;      // row 0: dwords d, d + 1
+  u32x3 r[4];    // row 1 + i: dwords 16 (1 + i) + d - 1, .. + d, .. + d + 1
+};
+
+// threadIdx.x, opaque to the compiler: lz4_tiles takes it once per block of
+// its run, so each block derives the lane constants of its phases again (as
+// a one-block workgroup does) instead of keeping them in ~60 registers
+// across the loop -- the kernel has 64 (8 waves per SIMD).
+__device__ __forceinline__ int block_lane() {
+  int lane = threadIdx.x;
+  asm volatile("" : "+v"(lane));
+  __builtin_assume(lane >= 0 && lane < 64);   // (what the opaque copy forgot: LDS offsets fold)
+  return lane;
+}
+
+__device__ __forceinline__ void load_keys(TileKeys &K, const uint8_t *__restrict__ src, int lane) {
+  typedef u32x2 u32x2_a4 __attribute__((aligned(4)));
+  typedef u32x3 u32x3_a4 __attribute__((aligned(4)));
+  const uint32_t *bw = reinterpret_cast<const uint32_t *>(src) + (lane >> 2);
+  K.r0 = *reinterpret_cast<const u32x2_a4 *>(bw);
+#pragma unroll
+  for (int r = 1; r < 5; ++r) K.r[r - 1] = *reinterpret_cast<const u32x3_a4 *>(bw + 16 * r - 1);
+}
+
+// The loaded dwords are used from here on: the compiler waits for K's loads
+// at this point (and nowhere later).  lz4_tiles places it where no younger
+// memory operation is in flight -- after a run's first, cold load, and in
+// every block before the records are stored.  Waited for at the top of the
+// next block instead, the loads' counter also held that block's record stores,
+// issued after them: each block then began by waiting for the stores of the
+// block before to be acknowledged (~2,000 cycles, LZ4R_PROF).
+__device__ __forceinline__ void keys_arrived(TileKeys &K) {
+  asm volatile("" : "+v"(K.r0), "+v"(K.r[0]), "+v"(K.r[1]), "+v"(K.r[2]), "+v"(K.r[3]));
+}
+
+// Encode one block (kFull: its dwords in K, the bytes at gsrc; otherwise n
+// bytes staged at S.buf[kInOff]) as sequence records:
 // dwords 0 .. kHeadW - 1 (header, records 0..22) at head, record k >= 23 at
 // ovf[k + 1 - kHeadW]; returns the bytes its stream takes.
 // kMatchesOnly: stop after the best-match scan and store every position's
 // find_longest_match result to mout instead (lz4r_block_matches_device).
+// next (kFull in a run, kTileRun > 1): the block whose dwords are loaded into K
+// once the index has consumed this block's, and fly during the rest of the
+// block -- the block the caller encodes next when that is a kFull block too,
+// else this block again (gsrc; never used, but the load is unconditional: no
+// branch in the index, and K has one definition per block).
 template <bool kMatchesOnly, bool kFull>
 __device__ __forceinline__ int encode_block(TileLds &S, int n_arg, const uint8_t *__restrict__ gsrc,
+                                            TileKeys &K, const uint8_t *__restrict__ next,
                                             uint32_t *__restrict__ mout,
                                             uint32_t *__restrict__ head,
                                             uint32_t *__restrict__ ovf,
-                                            uint32_t *__restrict__ status) {
+                                            uint32_t *__restrict__ status, const int lane,
+                                            ProfClock &prof) {
   // kFull: a whole 300-byte block of a 4-byte aligned input that is not the
   // launch's last (every block but one): n is a constant, only round 4's
   // lanes 41..63 hold positions past the last 4-gram start, and the block is
-  // NOT staged in LDS -- each lane loads the two dwords its 4-grams need
-  // straight from gsrc (L1/L2: the 24 bytes past the block end that row 4
-  // reads belong to the next block); otherwise the block is staged at
-  // S.buf[kInOff] by the caller.
+  // NOT staged in LDS -- each lane's 4-grams come from the dwords the caller
+  // (or the block before, see next) loaded straight from gsrc into K (the 24
+  // bytes past the block end that row 4 reads belong to the next block);
+  // otherwise the block is staged at S.buf[kInOff] by the caller.
   const int n = kFull ? kBlk : n_arg;
-  const int lane = threadIdx.x;
   constexpr int base = kInOff;
 
   // ---- index: per-bucket chains of the 4-gram starts -----------------------
@@ -85,7 +172,6 @@ __device__ __forceinline__ int encode_block(TileLds &S, int n_arg, const uint8_t
   // preceding byte (16..23) | tag (24..31: the position's own byte, which
   // equal 4-grams share).  Entries are written by ds_write_addtid_b32
   // (2 LDS cycles per round instead of 4-6 for a strided store).
-  PROF_DECL;
   const int nk = n >= 4 ? n - 3 : 0;     // positions that start a 4-gram
 
   bool walk[5];                          // p_r has a link (a walker)
@@ -94,17 +180,17 @@ __device__ __forceinline__ int encode_block(TileLds &S, int n_arg, const uint8_t
   {
     // bytes p .. p + 3 from two aligned dwords: sh = p & 3 = lane & 3
     const uint32_t sh = (uint32_t)lane & 3u;
-    const uint32_t *bw = kFull ? reinterpret_cast<const uint32_t *>(gsrc) + (lane >> 2)
-                               : reinterpret_cast<const uint32_t *>(S.buf) + (kInOff >> 2) +
-                                     (lane >> 2);
+    // (staged: the same dwords from LDS, one ds_read2_b32 per row and a
+    // ds_read_b32 for the dword before)
+    const uint32_t *bw = reinterpret_cast<const uint32_t *>(S.buf) + (kInOff >> 2) + (lane >> 2);
     uint32_t pt[5], adr[5], set[5];
     // inactive positions (p >= nk) exchange with a dword of rec[192 + lane]
     // (past the heads, zeroed after the exchanges; distinct per lane)
     const uint32_t dummy = (uint32_t)(kRecOff + 4 * (192 + lane) - kHeadOff);
 #pragma unroll
     for (int r = 0; r < 5; ++r) {
-      // one global_load_dwordx2 (kFull) or ds_read2_b32
-      const uint32_t w1 = bw[16 * r], w2 = bw[16 * r + 1];
+      const uint32_t w1 = !kFull ? bw[16 * r] : r ? K.r[r ? r - 1 : 0].y : K.r0.x;
+      const uint32_t w2 = !kFull ? bw[16 * r + 1] : r ? K.r[r ? r - 1 : 0].z : K.r0.y;
       key[r] = __builtin_amdgcn_alignbyte(w2, w1, sh);
       const uint32_t hv = key[r] * 2654435761u;                    // bucket = top 10 bits
       // [0, 0, blk[p - 1], blk[p]]: the entry without its link.  The tag
@@ -120,7 +206,7 @@ __device__ __forceinline__ int encode_block(TileLds &S, int n_arg, const uint8_t
       } else {
         // rows 1..4: bytes 3 + sh and 4 + sh of the dword pair before (one
         // more dword in the same load, no cross-lane step)
-        const uint32_t w0 = bw[16 * r - 1];
+        const uint32_t w0 = kFull ? K.r[r - 1].x : bw[16 * r - 1];
         pt[r] = __builtin_amdgcn_perm(w1, w0, 0x04030C0Cu + sh * 0x01010000u);
       }
       const int p = 64 * r + lane;
@@ -130,6 +216,15 @@ __device__ __forceinline__ int encode_block(TileLds &S, int n_arg, const uint8_t
       set[r] = (uint32_t)(4 * p);
     }
     if (lane == 0) pt[0] |= 1u << 15;     // p = 0: left-maximal with every later position
+    if (kFull && kTileRun > 1) {
+      // K is consumed once key[] and pt[] exist (pinned here: computed later,
+      // pt[] kept K's registers alive and the new dwords took others, copied
+      // back around the loop): the next block's dwords take K's registers and
+      // fly until that block's index
+#pragma unroll
+      for (int r = 0; r < 5; ++r) asm volatile("" : "+v"(key[r]), "+v"(pt[r]));
+      load_keys(K, next, lane);
+    }
     uint32_t old[5];
     xchg_rtn5(old, adr, set);
 #ifdef LZ4R_STALE_HEAD
@@ -415,6 +510,10 @@ __device__ __forceinline__ int encode_block(TileLds &S, int n_arg, const uint8_t
     wave_sync();
   }
   PROF_MARK(5);                       // walk
+  if (kFull && kTileRun > 1) {
+    keys_arrived(K);                  // the next block's: loaded since the index
+    PROF_MARK(7);
+  }
   // ---- sequence records: lane kk = sequence kk -----------------------------
   // A round is 64 consecutive sequences; the match sequences are a prefix
   // (cpos < n), followed by the literal-only tail when the last match ends
@@ -501,45 +600,71 @@ __device__ __forceinline__ int encode_block(TileLds &S, int n_arg, const uint8_t
   return ocar;
 }
 
+// (8 waves per SIMD = 64 VGPRs: around a loop the compiler would otherwise
+// keep every block-invariant lane constant in a register of its own)
 template <bool kAligned>   // the input is 4-byte aligned (the host checks)
-__global__ __launch_bounds__(64) void lz4_tiles(
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void lz4_tiles(
     const uint8_t *__restrict__ in, uint32_t nb, uint32_t per, uint32_t last_n,
     uint8_t *__restrict__ heads, uint8_t *__restrict__ ovfs, uint32_t *__restrict__ usz,
     uint16_t *__restrict__ bsizes, uint32_t *__restrict__ status) {
   __shared__ TileLds S;
-  const int lane = threadIdx.x;
+  ProfClock prof = PROF_START();
   // XCD-aware order: workgroups w and w + 8 share an XCD (observed round-robin
   // dealing), so XCD w % 8 takes the contiguous slice [(w % 8) per, ...) of
-  // the blocks and a 128-B line shared by two neighbouring blocks is fetched
-  // into one L2, not two (a speed matter only: any mapping is correct).
-  const uint32_t t = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
-  if (t >= nb) return;
-  const int n = t == nb - 1 ? (int)last_n : kBlk;
-  const uint8_t *src = in + (size_t)t * kBlk;
-
-  uint32_t *const head = reinterpret_cast<uint32_t *>(heads + (size_t)t * kHead);
-  uint32_t *const ovf = reinterpret_cast<uint32_t *>(ovfs + (size_t)t * kOvf);
-  int W;
-  if (kAligned && (t + 2 < nb || (t + 2 == nb && last_n >= 24))) {
-    // no staging, the keys come straight from global memory
-    // (encode_block<kFull>): row 4's lanes read 24 bytes past the block end
-    // (and a mid-walk lcp drain up to 15), so only where those bytes are the
-    // launch's own -- every block but the last, and the one before it when
-    // the last holds at least 24 bytes
-    W = encode_block<false, true>(S, kBlk, src, nullptr, head, ovf, status);
-  } else {
-    // the last block (n <= 300: nothing may be read past the input), the one
-    // before a last block of < 24 bytes, or an unaligned input: staged
-    // bytewise, 16-B zero pad
-    for (int i = lane; i < n; i += 64) S.buf[kInOff + i] = src[i];
-    if (lane < 16) S.buf[kInOff + n + lane] = 0;
-    wave_sync();
-    W = encode_block<false, false>(S, n, nullptr, nullptr, head, ovf, status);
+  // the blocks (per: a multiple of kTileRun) and a 128-B line shared by two
+  // neighbouring blocks is fetched into one L2, not two (a speed matter only:
+  // any mapping is correct).  Workgroup w takes run w / 8 of its slice.
+  const uint32_t t0 = (blockIdx.x & 7u) * per + (blockIdx.x >> 3) * (uint32_t)kTileRun;
+  if (t0 >= nb) return;
+  const uint32_t t1 = kTileRun == 1 ? t0 + 1 : min(t0 + (uint32_t)kTileRun, nb);
+  // Blocks that are not staged: the keys come straight from global memory
+  // (encode_block<kFull>): row 4's lanes read 24 bytes past the block end
+  // (and a mid-walk lcp drain up to 15), so only where those bytes are the
+  // launch's own -- every block but the last, and the one before it when
+  // the last holds at least 24 bytes: t + 2 < nb || (t + 2 == nb && last_n
+  // >= 24).  A prefix of the launch's blocks: when t is one, so is t - 1.
+  const uint32_t nbg = nb + (last_n >= 24 ? 1u : 0u);
+  auto full = [&](uint32_t t) { return kAligned && t + 2 < nbg; };
+  TileKeys K;
+  for (uint32_t t = t0; t < t1; ++t) {
+    const int lane = block_lane();
+    const int n = t == nb - 1 ? (int)last_n : kBlk;
+    const uint8_t *src = in + (size_t)t * kBlk;
+    uint32_t *const head = reinterpret_cast<uint32_t *>(heads + (size_t)t * kHead);
+    uint32_t *const ovf = reinterpret_cast<uint32_t *>(ovfs + (size_t)t * kOvf);
+    int W;
+    if (full(t)) {
+      // the run's first block waits for its own loads; every other finds its
+      // dwords in K, loaded during the block before (which was full too).
+      // The next block is prefetched only when it is a full block itself
+      // (otherwise this block's own dwords are loaded again, for nobody):
+      // no byte is read that a one-block workgroup would not read
+      if (t == t0) {
+        load_keys(K, src, lane);
+        keys_arrived(K);
+        PROF_MARK(7);                    // wave start .. the first block's keys are here
+      }
+      const bool pf = kTileRun > 1 && t + 1 < t1 && full(t + 1);
+      W = encode_block<false, true>(S, kBlk, src, K, pf ? src + kBlk : src, nullptr, head, ovf,
+                                    status, lane, prof);
+    } else {
+      // the last block (n <= 300: nothing may be read past the input), the one
+      // before a last block of < 24 bytes, or an unaligned input: staged
+      // bytewise, 16-B zero pad
+      for (int i = lane; i < n; i += 64) S.buf[kInOff + i] = src[i];
+      if (lane < 16) S.buf[kInOff + n + lane] = 0;
+      wave_sync();
+      if (t == t0) PROF_MARK(7);         // wave start .. the first block is staged
+      W = encode_block<false, false>(S, n, nullptr, K, nullptr, nullptr, head, ovf, status, lane,
+                                     prof);
+    }
+    if (lane == 0) {
+      usz[t] = (uint32_t)W;
+      bsizes[t] = (uint16_t)W;
+    }
+    wave_sync();   // the next block's LDS writes stay behind this block's reads
   }
-  if (lane == 0) {
-    usz[t] = (uint32_t)W;
-    bsizes[t] = (uint16_t)W;
-  }
+  PROF_FLUSH();
 }
 
 }  // namespace

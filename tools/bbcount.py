@@ -213,6 +213,17 @@ def build(src=None, name="prod", kernel=KERNEL):
     print(f"{len(bbs)} basic blocks, {sum(len(b) for _, b in bbs)} static instructions")
 
 
+def tile_grid(nb):
+    """(workgroups, blocks per XCD slice) of lz4_tiles' launch over nb blocks,
+    as run() in csrc/lz4r.hip computes them: a workgroup takes a run of
+    LZ4R_RUN blocks (the default in csrc/lz4r_layout.h, which the module is
+    built with), an XCD's slice is a whole number of runs."""
+    txt = open(os.path.join(REPO, "lz4-jpeg_amd", "csrc", "lz4r_layout.h")).read()
+    run = int(re.search(r"^#define LZ4R_RUN (\d+)", txt, re.M).group(1))
+    runs = (nb + 8 * run - 1) // (8 * run)
+    return 8 * runs, runs * run
+
+
 def _launch(hip, fn, grid, block, args):
     params = (ctypes.c_void_p * len(args))(*[ctypes.cast(ctypes.pointer(a), ctypes.c_void_p)
                                               for a in args])
@@ -263,9 +274,9 @@ def run_emit(outdir, name="prod", nbytes=1 << 30):
     assert hip.hipMemset(acc, 0, ctypes.c_size_t(4 * NCNT)) == 0
     P = lambda t: ctypes.c_void_p(t.data_ptr())
     U32, U64, I32 = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int32
-    per = (nb + 7) // 8
+    grid, per = tile_grid(nb)
     heads, ovfs = P(slots), ctypes.c_void_p(slots.data_ptr() + nb * 96)
-    _launch(hip, fns["lz4_tilesILb1EE"], 8 * per, 64,
+    _launch(hip, fns["lz4_tilesILb1EE"], grid, 64,
             [P(d_in), U32(nb), U32(per), U32(last_n), heads, ovfs, P(tsz), P(bsz), P(status)])
     _launch(hip, fns["lz4_scan_reduce"], npart, 256, [P(tsz), U64(nb), U64(0), P(gsum), P(part)])
     lenp = ctypes.c_void_p(status.data_ptr() + 8)
@@ -318,7 +329,7 @@ def run(outdir, name="prod", nbytes=1 << 30):
     assert hip.hipModuleGetGlobal(ctypes.byref(acc), ctypes.byref(accsz), mod,
                                   b"lz4r_bb_acc") == 0
     assert hip.hipMemset(acc, 0, ctypes.c_size_t(4 * NCNT)) == 0
-    per = (nb + 7) // 8
+    grid, per = tile_grid(nb)
     args = [ctypes.c_void_p(d_in.data_ptr()), ctypes.c_uint32(nb), ctypes.c_uint32(per),
             ctypes.c_uint32(last_n), ctypes.c_void_p(slots.data_ptr())]
     if "jjjPhS" in kname:             # (heads, overflow slots) since round 5
@@ -327,7 +338,7 @@ def run(outdir, name="prod", nbytes=1 << 30):
              ctypes.c_void_p(status.data_ptr())]
     params = (ctypes.c_void_p * len(args))(*[ctypes.cast(ctypes.pointer(a), ctypes.c_void_p)
                                               for a in args])
-    assert hip.hipModuleLaunchKernel(fn, 8 * per, 1, 1, 64, 1, 1, 0, None, params, None) == 0
+    assert hip.hipModuleLaunchKernel(fn, grid, 1, 1, 64, 1, 1, 0, None, params, None) == 0
     assert hip.hipDeviceSynchronize() == 0
     host = (ctypes.c_uint32 * NCNT)()
     assert hip.hipMemcpy(host, acc, ctypes.c_size_t(4 * NCNT), 2) == 0

@@ -1,6 +1,10 @@
 """Per-phase cycle shares of lz4_tiles from an LZ4R_PROF build
-(tools/build_variants.sh: tools/ab/liblz4_prof.so): run the 1 GiB corpus once to warm up,
-then `reps` calls, and print the summed s_memtime cycles of each phase."""
+(tools/build_variants.sh: tools/ab/liblz4_prof.so, or liblz4_prof_run1.so for a
+wave per block; chosen with LZ4JPEG_LIB): run the 1 GiB corpus once to warm up,
+then `reps` calls, and print the summed s_memtime cycles of each phase.
+"key wait" is the time from the wave's first instruction (a run's first
+block) or from the end of the block before (the others) until the block's
+key dwords have arrived: the cold loads, or what the prefetch left."""
 import ctypes
 import os
 import sys
@@ -11,7 +15,7 @@ import torch  # noqa: E402
 from lz4jpeg import _lib, lz4, synth  # noqa: E402
 
 PHASES = ["index", "walker queue", "candidates+lcp", "best scan", "nm+jump table", "walk",
-          "emission"]
+          "emission", "key wait"]
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1 << 30
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 d_in = torch.empty(n + 16, dtype=torch.uint8, device="cuda")

@@ -232,6 +232,51 @@ int jpegr_stream_decode_device(const void *d_in, size_t in_len, int w, int h, in
                                size_t tile0, size_t ntile, void *d_coef,
                                void *d_scratch, void *d_result, void *stream);
 
+/* The JPT1 stream: JPR1 with a tighter table coding.  Header ('J' 'P' 'T' '1'
+ * in place of the magic), u16 index, record order (Y, Cr, Cb), offsets by the
+ * exclusive scan of the index and little-endian fields are JPR1's.  A stream:
+ *   u8 rle_len | u8 ncodes | u16 f        nbits = f & 0x3FFF, mode = f >> 14
+ *   table, by mode:
+ *     0  ncodes x { i16 value, u8 code_length }            (JPR1's entries)
+ *     1  ceil(ncodes / 2) length bytes, then ncodes x i8 value
+ *     2  ceil(ncodes / 2) length bytes, then ncodes x i16 value
+ *     3  malformed
+ *   ceil(nbits / 8) bytes of bits, as JPR1
+ * Entry k's code length is the low nibble of length byte k / 2 for even k, the
+ * high nibble for odd k; with an odd ncodes the last high nibble is written
+ * as 0 and ignored by readers.  Entries are in the table's (DFS) order and the
+ * codes follow from the lengths as stated for d_table above; bits 24..31 of a
+ * table word do not reach the stream.
+ * The writer's mode is canonical, so the bytes are deterministic: mode 1 when
+ * ncodes > 0, every length is <= 15 and every value is in -128..127; else
+ * mode 2 when ncodes > 0 and every length is <= 15; else mode 0 (a meta field
+ * past its slot is clamped first, as in jpegr_pack_device).  Readers accept
+ * any of modes 0..2 on any stream.  A mode-0 stream is byte for byte a JPR1
+ * stream, and modes 1 and 2 are never longer: a record is at most 1,036 B,
+ * jpegr_pack_bound serves both formats, and the record rules are JPR1's (a
+ * stream's rle_len, ncodes or nbits past its slot, a mode of 3, or three
+ * streams that do not sum to the indexed size: malformed).
+ *
+ * jpegr_pack_tight_device: jpegr_pack_device's arguments and contract
+ * (asynchronous, no read-back, no host state, capturable; a u64 length or
+ * needed capacity at d_out_len; nothing written at or past cap; JPEGR_ERR_ARG
+ * before any HIP call), writing a JPT1 stream.  d_scratch:
+ * jpegr_pack_scratch_bytes.
+ * jpegr_stream_format (host only): w, h, nimg and the format of a header's 16
+ * bytes, JPEGR_STREAM_JPR1 or JPEGR_STREAM_JPT1; JPEGR_ERR_ARG on any other
+ * magic, a zero dimension or a NULL pointer.  jpegr_stream_info keeps
+ * rejecting everything but JPR1.
+ * jpegr_stream_decode_device takes either format, told by the magic, with
+ * every guarantee above.  jpegr_unpack_device does not: a JPT1 stream is a
+ * wrong magic to it (verdict 0), so slots from a JPT1 stream are not offered,
+ * and decompress_device (lz4jpeg.jpeg) raises on one. */
+#define JPEGR_STREAM_JPR1 1
+#define JPEGR_STREAM_JPT1 2
+int jpegr_pack_tight_device(const void *d_bits, const void *d_meta, const void *d_table,
+                            int w, int h, int nimg, void *d_out, size_t cap,
+                            void *d_out_len, void *d_scratch, void *stream);
+int jpegr_stream_format(const uint8_t header[16], int *w, int *h, int *nimg, int *format);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,9 @@
-// jpegr_stream.hip -- entropy decode straight from the JPR stream
-// (include/jpegr.h): tiles [tile0, tile0 + ntile) of a stream to coefficients,
-// no slots in between.
+// jpegr_stream.hip -- entropy decode straight from the JPR stream, JPR1 or
+// JPT1 (include/jpegr.h): tiles [tile0, tile0 + ntile) of a stream to
+// coefficients, no slots in between.  The format is the header's, one for the
+// launch: jprs_decode branches once into the record routine of that format
+// (decode_record<kTight>; the JPR1 instantiation is the code it was before JPT1
+// existed).
 //
 //   jprs_sizes    index -> u32 sizes (the scan's input), the header verdict in
 //                 result[1], result[2] = 0: the call's first launch initialises
@@ -52,7 +55,7 @@ __global__ __launch_bounds__(256) void jprs_sizes(const uint8_t *__restrict__ in
     const uint32_t want[4] = {0x3152504Au /* "JPR1" */, w, h, nimg};
     bool ok = in_len >= kHdr + 2 * (uint64_t)ntiles;
     for (uint32_t i = 0; ok && i < (uint32_t)kHdr; ++i)
-      ok = in[i] == (uint8_t)(want[i >> 2] >> (8 * (i & 3)));
+      ok = in[i] == (uint8_t)(want[i >> 2] >> (8 * (i & 3))) || (i == 2 && in[i] == 'T');   // or "JPT1"
     result[1] = ok ? ~0ull : 0ull;
     result[2] = 0ull;
   }
@@ -139,15 +142,26 @@ __device__ __forceinline__ uint32_t scount_above(uint32_t w, const uint32_t (&h)
 // lie inside it; nothing else is read: a table index is clamped to U - 1 and
 // a bit byte past nby reads sp[0] instead (in bounds, and what lies past the
 // bits cannot change a decode: see lookup).
-struct StreamSrc {
+template <bool kTight>
+struct StreamSrc;
+
+template <>
+struct StreamSrc<false> {
   const uint8_t *sp, *pb;
   int U, nby;
-  __device__ __forceinline__ StreamSrc(const uint8_t *s, uint32_t m)
+  __device__ __forceinline__ StreamSrc(const uint8_t *s, uint32_t m, uint32_t)
       : sp(s), pb(s + 4 + 3 * (m >> 24)), U((int)(m >> 24)), nby((int)(((m & 0xFFFFu) + 7u) >> 3)) {}
   // entry k as d_table's word: value | length << 16 (k < U)
   __device__ __forceinline__ uint32_t entry(int k) const {
     const uint8_t *e = sp + 4 + 3 * k;
     return (uint32_t)e[0] | (uint32_t)e[1] << 8 | (uint32_t)e[2] << 16;
+  }
+  __device__ __forceinline__ int len(int k) const { return (int)sp[4 + 3 * k + 2]; }
+  // the table's first min(U, Cap) entries, all loads issued before any is used
+  template <int Cap>
+  __device__ __forceinline__ void head(uint32_t (&tb)[Cap]) const {
+#pragma unroll
+    for (int k = 0; k < Cap; ++k) tb[k] = entry(min(k, U - 1));
   }
   __device__ __forceinline__ uint32_t byte(int j) const { return *(j < nby ? pb + j : sp); }
   // bit bytes j .. j + 3, the first in the top byte (MSB-first bits)
@@ -156,18 +170,73 @@ struct StreamSrc {
   }
 };
 
+// A stream of a JPT1 record: its table by mode (0: JPR1's 3-B entries; 1, 2:
+// ceil(U / 2) bytes of nibble lengths at sp + 4, then U values of 1 or 2 B at
+// pv), then the bit bytes at pb.  The same rules: a table index is clamped to
+// U - 1, so every read lies inside the stream's own checked bytes.
+template <>
+struct StreamSrc<true> {
+  const uint8_t *sp, *pv, *pb;
+  int U, nby;
+  uint32_t mode;
+  __device__ __forceinline__ StreamSrc(const uint8_t *s, uint32_t m, uint32_t md)
+      : sp(s), U((int)(m >> 24)), nby((int)(((m & 0xFFFFu) + 7u) >> 3)), mode(md) {
+    pv = s + 4 + (md ? (U + 1) >> 1 : 0);
+    pb = pv + (md ? (int)md * U : 3 * U);
+  }
+  __device__ __forceinline__ int len(int k) const {
+    return mode == 0 ? (int)sp[4 + 3 * k + 2] : (int)((sp[4 + (k >> 1)] >> (4 * (k & 1))) & 15u);
+  }
+  __device__ __forceinline__ uint32_t value(int k) const {     // the i16 as d_table's low half
+    if (mode == 1) return (uint32_t)(uint16_t)(int8_t)pv[k];
+    const uint8_t *e = pv + (mode ? 2 : 3) * k;
+    return (uint32_t)e[0] | (uint32_t)e[1] << 8;
+  }
+  __device__ __forceinline__ uint32_t entry(int k) const { return value(k) | (uint32_t)len(k) << 16; }
+  // A length byte is loaded once for its pair of entries: entry k + 1 past
+  // U - 1 is never used, so the pair's upper nibble may stand for it.
+  template <int Cap>
+  __device__ __forceinline__ void head(uint32_t (&tb)[Cap]) const {
+    static_assert(Cap % 2 == 0, "pairs of entries");
+    if (mode == 1) {
+#pragma unroll
+      for (int k = 0; k < Cap; k += 2) {
+        const uint32_t lb = sp[4 + (min(k, U - 1) >> 1)];
+        tb[k] = (uint32_t)(uint16_t)(int8_t)pv[min(k, U - 1)] | (lb & 15u) << 16;
+        tb[k + 1] = (uint32_t)(uint16_t)(int8_t)pv[min(k + 1, U - 1)] | (lb >> 4) << 16;
+      }
+    } else if (mode == 2) {
+#pragma unroll
+      for (int k = 0; k < Cap; k += 2) {
+        const uint32_t lb = sp[4 + (min(k, U - 1) >> 1)];
+        const uint8_t *e0 = pv + 2 * min(k, U - 1), *e1 = pv + 2 * min(k + 1, U - 1);
+        tb[k] = (uint32_t)e0[0] | (uint32_t)e0[1] << 8 | (lb & 15u) << 16;
+        tb[k + 1] = (uint32_t)e1[0] | (uint32_t)e1[1] << 8 | (lb >> 4) << 16;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < Cap; ++k) {
+        const uint8_t *e = sp + 4 + 3 * min(k, U - 1);
+        tb[k] = (uint32_t)e[0] | (uint32_t)e[1] << 8 | (uint32_t)e[2] << 16;
+      }
+    }
+  }
+  __device__ __forceinline__ uint32_t byte(int j) const { return *(j < nby ? pb + j : sp); }
+  __device__ __forceinline__ uint32_t be32(int j) const {
+    return byte(j) << 24 | byte(j + 1) << 16 | byte(j + 2) << 8 | byte(j + 3);
+  }
+};
+
 // decode_stream of jpegr_entropy.hip (its comments hold there): returns 1
 // (decoded), 0 (malformed) or -1 (a value or length that the u16 entries
 // cannot hold, or codes that do not increase: sdecode_slow).  1 <= U <= Cap.
-template <int Cap, typename VlT>
-__device__ int sdecode(const StreamSrc &S, uint32_t m, VlT vl, int16_t *__restrict__ out, int n,
+template <int Cap, typename Src, typename VlT>
+__device__ int sdecode(const Src &S, uint32_t m, VlT vl, int16_t *__restrict__ out, int n,
                        uint32_t *bm) {
   const int nbits = (int)(m & 0xFFFF), R = (int)((m >> 16) & 255), U = (int)(m >> 24);
   if (R == 0 || R > 2 * n) return 0;
-  // the table's first min(U, Cap) entries, all loads issued before any is used
   uint32_t tb[Cap];
-#pragma unroll
-  for (int k = 0; k < Cap; ++k) tb[k] = S.entry(min(k, U - 1));
+  S.head(tb);
   uint32_t lh[Cap];
   uint32_t code = 0, prev = 0;
   int plen = 0, lmax = 0;
@@ -300,7 +369,8 @@ __device__ int sdecode(const StreamSrc &S, uint32_t m, VlT vl, int16_t *__restri
 // decode_stream_slow of jpegr_entropy.hip: more codes than the registers hold,
 // or a table the fast walk cannot take.  The codes are regenerated from the
 // stream's own table bytes for every symbol.
-__device__ bool sdecode_slow(const StreamSrc &S, uint32_t m, int16_t *__restrict__ out, int n) {
+template <typename Src>
+__device__ bool sdecode_slow(const Src &S, uint32_t m, int16_t *__restrict__ out, int n) {
   const int nbits = (int)(m & 0xFFFF), R = (int)((m >> 16) & 255), U = (int)(m >> 24);
   if (R == 0 || R > 2 * n) return false;
   int p = 0, got = 0, idx = 0, pending = 0;
@@ -313,7 +383,7 @@ __device__ bool sdecode_slow(const StreamSrc &S, uint32_t m, int16_t *__restrict
     uint32_t code = 0;
     int plen = 0, hit = -1, L = 0;
     for (int k = 0; k < U && hit < 0; ++k) {
-      L = (int)S.sp[4 + 3 * k + 2];
+      L = S.len(k);
       if (L == 0 || L > 32) return false;
       if (k) code = L >= plen ? (code + 1) << (L - plen) : (code + 1) >> (plen - L);
       plen = L;
@@ -341,12 +411,13 @@ __device__ bool sdecode_slow(const StreamSrc &S, uint32_t m, int16_t *__restrict
 // One wave's lanes of one channel group.  rec: the lane's record in the
 // stream; so / m: its streams' offsets in the record and meta words;
 // good: the record is well-formed (else its ints are 0 and nothing of it is
-// read).  Returns the lane's rejected streams.
-template <bool kLuma>
+// read); md: the streams' table modes, Y | Cr << 2 | Cb << 4 (JPT1).  Returns
+// the lane's rejected streams.
+template <bool kLuma, bool kTight>
 __device__ __forceinline__ uint32_t sdecode_wave(SDecLds<kLuma ? 64 : 32, kLuma ? kFastCap : kChromaCap> &S,
                                                  int lane, const uint8_t *rec, bool good,
                                                  const uint32_t (&so)[3], const uint32_t (&m)[3],
-                                                 int16_t *__restrict__ tile_out) {
+                                                 uint32_t md, int16_t *__restrict__ tile_out) {
   constexpr int Cap = kLuma ? kFastCap : kChromaCap;
   uint32_t fails = 0;
   int16_t *o = S.out[lane];
@@ -358,7 +429,7 @@ __device__ __forceinline__ uint32_t sdecode_wave(SDecLds<kLuma ? 64 : 32, kLuma 
     const int n = stream_len(c);
     bool ok = false;
     if (good) {
-      const StreamSrc src(rec + oc, mc);
+      const StreamSrc<kTight> src(rec + oc, mc, (md >> (2 * c)) & 3u);
       const int U = (int)(mc >> 24);
       const int r = U == 0 ? 0
                     : U <= Cap ? sdecode<Cap>(src, mc, vl, o, n, kLuma ? &S.bm[0][lane] : nullptr)
@@ -376,6 +447,54 @@ __device__ __forceinline__ uint32_t sdecode_wave(SDecLds<kLuma ? 64 : 32, kLuma 
   return fails;
 }
 
+// A lane's record of `size` bytes at rec, tile t of the stream: the three
+// stream headers against the slots' bounds and the indexed size
+// (jpr_unpack_tiles' record rules; in a JPT1 record the table's bytes follow
+// from the mode in the top two bits of the u16, and mode 3 is malformed); each
+// header is read only once it is known to lie inside the record.  Then the
+// wave's channel group is decoded.
+template <bool kTight>
+__device__ __forceinline__ void decode_record(SDecLds<64, kFastCap> &SY, SDecLds<32, kChromaCap> &SC,
+                                              int lane, int wv, const uint8_t *rec, uint32_t size,
+                                              size_t t, uint64_t *__restrict__ result,
+                                              int16_t *__restrict__ tile_out) {
+  bool good = size <= (uint32_t)kRecMax;
+  uint32_t p = 0, so[3] = {0u, 0u, 0u}, m[3] = {0u, 0u, 0u}, md = 0u;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    good = good && p + 4 <= size;
+    if (good) {
+      const uint32_t rle = rec[p], nc = rec[p + 1];
+      uint32_t nb = (uint32_t)rec[p + 2] | (uint32_t)rec[p + 3] << 8;
+      uint32_t tbytes = 3u * nc;
+      if constexpr (kTight) {
+        const uint32_t mode = nb >> 14;
+        nb &= 0x3FFFu;
+        good = mode != 3u;
+        if (mode) tbytes = ((nc + 1u) >> 1) + mode * nc;
+        md |= mode << (2 * c);
+      }
+      good = good && rle <= slot_codes(c) && nc <= slot_codes(c) && nb <= slot_bits(c);
+      so[c] = p;
+      m[c] = nb | rle << 16 | nc << 24;
+      p += 4u + tbytes + ((nb + 7u) >> 3);
+    }
+  }
+  good = good && p == size;
+  uint32_t fails;
+  if (__builtin_amdgcn_readfirstlane(wv) == 0) {
+    if (!good)
+      atomicMin(reinterpret_cast<unsigned long long *>(result + 1), 1ull + (unsigned long long)t);
+    fails = sdecode_wave<true, kTight>(SY, lane, rec, good, so, m, md, tile_out);
+  } else {
+    fails = sdecode_wave<false, kTight>(SC, lane, rec, good, so, m, md, tile_out);
+  }
+  // the wave's rejected streams: one add, after jprs_sizes' zero in stream order
+  const uint32_t f = (uint32_t)__popcll(__ballot(fails & 1)) + 2u * (uint32_t)__popcll(__ballot(fails & 2));
+  if (f && lane == __builtin_ctzll(__ballot(1)))
+    atomicAdd(reinterpret_cast<unsigned long long *>(result + 2), (unsigned long long)f);
+}
+
 __global__ __launch_bounds__(2 * kLanes) void jprs_decode(
     const uint8_t *__restrict__ in, uint64_t in_len, size_t ntiles, size_t tile0, size_t ntile,
     size_t wg_base, const uint32_t *__restrict__ tsz, const uint32_t *__restrict__ gsum,
@@ -389,6 +508,7 @@ __global__ __launch_bounds__(2 * kLanes) void jprs_decode(
   const int ntl = (int)min((size_t)kLanes, ntile - first);
   int16_t *const wg_out = coef + first * 128;
   const uint64_t implied = result[0], head = result[1];
+  const uint32_t fmt = in_len >= (uint64_t)kHdr ? in[2] : 0u;   // 'R' or 'T' when head != 0
   if (head == 0 || implied != in_len) {                     // the same in every workgroup
     uint4 *dst = reinterpret_cast<uint4 *>(wg_out);
     for (int i = tid; i < ntl * 16; i += 2 * kLanes) dst[i] = make_uint4(0u, 0u, 0u, 0u);
@@ -410,40 +530,13 @@ __global__ __launch_bounds__(2 * kLanes) void jprs_decode(
   if (lane >= ntl) return;
   // implied == in_len: every offset of the scan lies inside the stream
   const uint8_t *rec = in + (base + inc - size);
-  // the three stream headers against the slots' bounds and the indexed size
-  // (jpr_unpack_tiles' record rules); each header is read only once it is
-  // known to lie inside the record
-  bool good = size <= (uint32_t)kRecMax;
-  uint32_t p = 0, so[3] = {0u, 0u, 0u}, m[3] = {0u, 0u, 0u};
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    good = good && p + 4 <= size;
-    if (good) {
-      const uint32_t rle = rec[p], nc = rec[p + 1];
-      const uint32_t nb = (uint32_t)rec[p + 2] | (uint32_t)rec[p + 3] << 8;
-      good = rle <= slot_codes(c) && nc <= slot_codes(c) && nb <= slot_bits(c);
-      so[c] = p;
-      m[c] = nb | rle << 16 | nc << 24;
-      p += 4u + 3u * nc + ((nb + 7u) >> 3);
-    }
-  }
-  good = good && p == size;
   int16_t *const tile_out = wg_out + (size_t)lane * 128;
-  uint32_t fails;
-  if (__builtin_amdgcn_readfirstlane(wv) == 0) {
-    if (!good)
-      atomicMin(reinterpret_cast<unsigned long long *>(result + 1),
-                1ull + (unsigned long long)(a + lane));
-    fails = sdecode_wave<true>(SY, lane, rec, good, so, m, tile_out);
-  } else {
-    fails = sdecode_wave<false>(SC, lane, rec, good, so, m, tile_out);
-  }
-  // the wave's rejected streams: one add, after jprs_sizes' zero in stream order
-  const uint32_t f = (uint32_t)__popcll(__ballot(fails & 1)) + 2u * (uint32_t)__popcll(__ballot(fails & 2));
-  if (f && lane == __builtin_ctzll(__ballot(1)))
-    atomicAdd(reinterpret_cast<unsigned long long *>(result + 2), (unsigned long long)f);
+  // the stream's format, from the header jprs_sizes accepted: one for the launch
+  if (__builtin_amdgcn_readfirstlane(fmt) == 'T')
+    decode_record<true>(SY, SC, lane, wv, rec, size, a + lane, result, tile_out);
+  else
+    decode_record<false>(SY, SC, lane, wv, rec, size, a + lane, result, tile_out);
 }
-
 }  // namespace
 
 extern "C" int jpegr_stream_decode_device(const void *d_in, size_t in_len, int w, int h, int nimg,

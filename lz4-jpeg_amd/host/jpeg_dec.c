@@ -1,10 +1,10 @@
 /*
- * JPEG_dec -- one image of a JPR stream (include/jpegr.h; JPEG_seq's
- * coefficients.jpr) back to pixels:
+ * JPEG_dec -- one image of a JPR1 or JPT1 stream (include/jpegr.h; JPEG_seq's
+ * coefficients.jpr, or jpegr_pack_tight_device's output) back to pixels:
  *
  *   JPEG_dec <in.jpr> <out.png> [image]
  *
- * The dimensions come from the stream's header (jpegr_stream_info); image
+ * The dimensions come from the stream's header (jpegr_stream_format); image
  * `image` (default 0) is the tile range [image * tiles, (image + 1) * tiles)
  * of the stream, entropy-decoded straight from the stream's bytes
  * (jpegr_stream_decode_device: no slots) and reconstructed
@@ -48,8 +48,9 @@ int main(int argc, char **argv) {
   if (fread(data, 1, (size_t)flen, f) != (size_t)flen) fail("cannot read the input file");
   fclose(f);
 
-  int w = 0, h = 0, nimg = 0;
-  if (jpegr_stream_info(data, &w, &h, &nimg) != JPEGR_OK) fail("not a JPR stream (bad header)");
+  int w = 0, h = 0, nimg = 0, format = 0;
+  if (jpegr_stream_format(data, &w, &h, &nimg, &format) != JPEGR_OK)
+    fail("not a JPR stream (bad header)");
   if (image >= nimg) fail("image index out of range");
   const size_t per = jpegr_coef_count(w, h) / 128;          /* tiles of one image */
   const size_t ntiles = jpegr_pack_bound(w, h, nimg) ? per * (size_t)nimg : 0;

@@ -58,6 +58,9 @@ SIGNATURES = [
     ("jpegr_unpack_device", _i, [_vp, _c_size, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("jpegr_stream_decode_device", _i, [_vp, _c_size, _i, _i, _i, _c_size, _c_size, _vp, _vp, _vp,
                                         _vp]),
+    ("jpegr_pack_tight_device", _i, [_vp, _vp, _vp, _i, _i, _i, _vp, _c_size, _vp, _vp, _vp]),
+    ("jpegr_stream_format", _i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i),
+                                 ctypes.POINTER(_i)]),
     ("jpegr_planes_device", _i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     ("jpegr_dct_blocks_device", _i, [_vp, _i, _i, _i, _vp, _vp]),
     ("jpegr_quantize_device", _i, [_vp, _vp, _i, _c_size, _vp]),

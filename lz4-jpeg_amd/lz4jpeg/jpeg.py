@@ -143,6 +143,7 @@ class Entropy:
 
 # ---- the JPR stream (include/jpegr.h): the entropy stage's output as bytes ------
 PACK_RECORD_MAX = 1036
+STREAM_JPR1, STREAM_JPT1 = 1, 2           # jpegr_stream_format's formats
 
 
 def pack_bound(w, h, nimg=1):
@@ -155,8 +156,9 @@ def _pack_scratch(ntiles, device):
                        device=device)
 
 
-def pack_device(ent, w, h, nimg=1, d_out=None, stream=None, d_len=None, scratch=None):
-    """Pack an Entropy's slots into one JPR stream.  Returns (d_out, d_len):
+def pack_device(ent, w, h, nimg=1, d_out=None, stream=None, d_len=None, scratch=None, tight=False):
+    """Pack an Entropy's slots into one JPR stream -- JPR1, or with tight=True
+    JPT1, the tighter table coding (jpegr.h).  Returns (d_out, d_len):
     d_out a uint8 tensor (pack_bound bytes when not given), d_len a one-element
     int64 tensor holding the stream length -- or the capacity needed when that
     exceeds d_out's size, in which case nothing past d_out is written.
@@ -171,13 +173,14 @@ def pack_device(ent, w, h, nimg=1, d_out=None, stream=None, d_len=None, scratch=
         d_len = torch.zeros(1, dtype=torch.int64, device=dev)
     if scratch is None:
         scratch = _pack_scratch(ent.ntiles, dev)
-    rc = _lib.lib().jpegr_pack_device(
+    fn = _lib.lib().jpegr_pack_tight_device if tight else _lib.lib().jpegr_pack_device
+    rc = fn(
         ctypes.c_void_p(ent.bits.data_ptr()), ctypes.c_void_p(ent.meta.data_ptr()),
         ctypes.c_void_p(ent.table.data_ptr()), w, h, nimg, ctypes.c_void_p(d_out.data_ptr()),
         d_out.numel(), ctypes.c_void_p(d_len.data_ptr()), ctypes.c_void_p(scratch.data_ptr()),
         _stream_handle(stream))
     if rc != 0:
-        raise JpegError(rc, "jpegr_pack_device")
+        raise JpegError(rc, "jpegr_pack_tight_device" if tight else "jpegr_pack_device")
     return d_out, d_len
 
 
@@ -224,9 +227,24 @@ def stream_info(header_bytes):
     return w.value, h.value, n.value
 
 
+def stream_format(header_bytes):
+    """(w, h, nimg, tight) of the first 16 bytes of a JPR1 (tight False) or
+    JPT1 (tight True) stream; JpegError on any other magic or a zero
+    dimension."""
+    hdr = bytes(header_bytes[:16])
+    if len(hdr) < 16:
+        raise ValueError("a JPR header is 16 bytes")
+    w, h, n, fmt = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    rc = _lib.lib().jpegr_stream_format(ctypes.c_char_p(hdr), ctypes.byref(w), ctypes.byref(h),
+                                        ctypes.byref(n), ctypes.byref(fmt))
+    if rc != 0:
+        raise JpegError(rc, "jpegr_stream_format")
+    return w.value, h.value, n.value, fmt.value == STREAM_JPT1
+
+
 def decode_stream_device(d_stream, in_len, w, h, nimg=1, tile0=0, ntiles=None, d_coef=None,
                          d_result=None, scratch=None, stream=None):
-    """Tiles [tile0, tile0 + ntiles) of a JPR stream's first in_len bytes
+    """Tiles [tile0, tile0 + ntiles) of a JPR1 or JPT1 stream's first in_len bytes
     straight to coefficients (jpegr_stream_decode_device: no slots; ntiles
     None = up to the stream's last tile).  Returns (d_coef, d_result): d_coef
     int16, 128 per selected tile; d_result three int64 on the device, [0] the
@@ -260,7 +278,7 @@ def decode_stream_device(d_stream, in_len, w, h, nimg=1, tile0=0, ntiles=None, d
 
 
 def decompress_images_device(d_stream, first=0, count=None):
-    """Images [first, first + count) of a JPR stream (uint8 tensor, exactly
+    """Images [first, first + count) of a JPR1 or JPT1 stream (uint8 tensor, exactly
     the stream; count None = up to the last) -> (rgba uint8 tensor, w, h,
     count): reads the 16 header bytes back, decodes the images' tile range
     straight from the stream and reconstructs it (every tile decoded, as
@@ -269,7 +287,7 @@ def decompress_images_device(d_stream, first=0, count=None):
     (d_result[2] != 0)."""
     if d_stream.numel() < 16:
         raise JpegError(-1, "decompress_images_device: shorter than a header")
-    w, h, nimg = stream_info(d_stream[:16].cpu().numpy().tobytes())
+    w, h, nimg, _ = stream_format(d_stream[:16].cpu().numpy().tobytes())
     if count is None:
         count = nimg - first
     if first < 0 or count <= 0 or first + count > nimg:
@@ -286,15 +304,17 @@ def decompress_images_device(d_stream, first=0, count=None):
     return out, w, h, count
 
 
-def compress_device(d_rgba, w, h, nimg=1):
-    """RGBA8 images -> a uint8 tensor of exactly the JPR stream: encode,
-    entropy encode, pack; the length is read back once, then the encoder's
+def compress_device(d_rgba, w, h, nimg=1, tight=False):
+    """RGBA8 images -> a uint8 tensor of exactly the JPR stream (JPR1, or JPT1
+    with tight=True: the same content in fewer bytes, read by
+    decompress_images_device and decode_stream_device only): encode, entropy
+    encode, pack; the length is read back once, then the encoder's
     status word.  Raises JpegError if a stream overflowed the reference's
     buffers (status[0] != 0)."""
     d_coef = encode_device(d_rgba, w, h, nimg)
     ent = Entropy(nimg * tiles(w, h), device=d_rgba.device)
     ent.encode(d_coef)
-    d_out, d_len = pack_device(ent, w, h, nimg)
+    d_out, d_len = pack_device(ent, w, h, nimg, tight=tight)
     n = int(d_len.item())
     if int(ent.status[0].item()) != 0:
         raise JpegError(-1, "compress_device: a stream overflows the reference's buffers")
@@ -302,7 +322,8 @@ def compress_device(d_rgba, w, h, nimg=1):
 
 
 def decompress_device(d_stream):
-    """A JPR stream (uint8 tensor, exactly the stream) -> (rgba uint8 tensor,
+    """A JPR1 stream (uint8 tensor, exactly the stream; a JPT1 stream raises
+    JpegError: it has no slot form) -> (rgba uint8 tensor,
     w, h, nimg): reads the 16 header bytes back, then unpack, entropy decode
     and reconstruct.  No d_orig is passed to the reconstruction, so every tile
     is decoded (the reference leaves its trailing tiles untransformed; see

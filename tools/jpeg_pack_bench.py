@@ -4,7 +4,7 @@ jpeg.compress_device on an MI355X; bench.py's discipline: a clock pre-warm,
 settle() on each measured call, then event-timed means over back-to-back
 launches.
 
-    python tools/jpeg_pack_bench.py [--steps K] [--once N]
+    python tools/jpeg_pack_bench.py [--steps K] [--once N] [--decode | --tight [--against LIB]]
 
 Images: bench.py's 3840x2160 random image (synth.rand_rgba_device, seed 1)
 and a 3840x2160 smooth one (tests/test_gpu_entropy.py's generator).  Prints
@@ -23,7 +23,17 @@ repeats of the same call is known before a difference is read; then one image
 of an 8-image stream (the random image eight times) against the two stages
 over the whole of that stream, which is the only way to that image without
 the direct decode; and the device bytes a 4K decode needs either way.  With
---once N: N direct decodes per image and nothing else."""
+--once N: N direct decodes per image and nothing else.
+
+--tight: the JPT1 stream beside JPR1, for profiles/jpt_pack_bench.log: both
+packs and the direct decode of each stream, alternated over --rounds rounds in
+this run after the same pre-warm and settle; both streams' lengths and bytes
+per tile; every output checked (the tight stream decodes to the coefficients
+the entropy stage was given).  --against LIB adds the JPR1 calls -- pack,
+unpack, direct decode -- of a second build of the library (the parent
+commit's, loaded beside the product's with RTLD_LOCAL) to the same rounds, and
+prints each pair with the ratio of the medians.  With --once N: N launches of
+the two packs and the two direct decodes per image and nothing else."""
 import argparse
 import json
 import os
@@ -165,12 +175,132 @@ def decode_side(args, torch, jpeg, name, img, d_coef, d_out, n, back, d_res, s2,
     print(json.dumps(out), flush=True)
 
 
+class Calls:
+    """The stream calls of one build of the library on one image's slots, each
+    with buffers of its own."""
+
+    def __init__(self, lib, torch, ent, nt, d_coef):
+        import ctypes
+        from lz4jpeg import _lib, jpeg
+        self.lib, self.ent, self.nt, self.c = lib, ent, nt, ctypes
+        for fname, res, argt in _lib.SIGNATURES:
+            if fname.startswith("jpegr_") and hasattr(lib, fname):
+                fn = getattr(lib, fname)
+                fn.restype, fn.argtypes = res, argt
+        dev = d_coef.device
+        self.st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        nscr = int(lib.jpegr_pack_scratch_bytes(nt))
+        self.scr = [torch.empty(nscr, dtype=torch.uint8, device=dev) for _ in range(5)]
+        self.out = torch.empty(int(lib.jpegr_pack_bound(W, H, 1)), dtype=torch.uint8, device=dev)
+        self.out_t = torch.empty_like(self.out)
+        self.len = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.len_t = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.back = jpeg.Entropy(nt, device=dev)
+        self.res2 = torch.zeros(2, dtype=torch.int64, device=dev)
+        self.res3 = torch.zeros(3, dtype=torch.int64, device=dev)
+        self.res3_t = torch.zeros(3, dtype=torch.int64, device=dev)
+        self.coef = torch.empty_like(d_coef)
+        self.coef_t = torch.empty_like(d_coef)
+        self.n = self.n_t = 0
+
+    def _p(self, t):
+        return self.c.c_void_p(t.data_ptr())
+
+    def _pack(self, fn, out, d_len, scr):
+        e = self.ent
+        rc = fn(self._p(e.bits), self._p(e.meta), self._p(e.table), W, H, 1, self._p(out), out.numel(),
+                self._p(d_len), self._p(scr), self.st)
+        assert rc == 0, rc
+
+    def _direct(self, src, n, coef, res, scr):
+        rc = self.lib.jpegr_stream_decode_device(self._p(src), n, W, H, 1, 0, self.nt, self._p(coef),
+                                                 self._p(scr), self._p(res), self.st)
+        assert rc == 0, rc
+
+    def pack(self):
+        self._pack(self.lib.jpegr_pack_device, self.out, self.len, self.scr[0])
+
+    def pack_tight(self):
+        self._pack(self.lib.jpegr_pack_tight_device, self.out_t, self.len_t, self.scr[1])
+
+    def unpack(self):
+        b = self.back
+        rc = self.lib.jpegr_unpack_device(self._p(self.out), self.n, W, H, 1, self._p(b.bits),
+                                          self._p(b.meta), self._p(b.table), self._p(self.scr[2]),
+                                          self._p(self.res2), self.st)
+        assert rc == 0, rc
+
+    def direct(self):
+        self._direct(self.out, self.n, self.coef, self.res3, self.scr[3])
+
+    def direct_tight(self):
+        self._direct(self.out_t, self.n_t, self.coef_t, self.res3_t, self.scr[4])
+
+
+def tight_side(args, torch, jpeg, name, ent, d_coef, other):
+    """JPR1 and JPT1 pack and direct decode, and the JPR1 calls of `other`
+    (a second build's ctypes handle, or None): same run, alternated."""
+    nt = jpeg.tiles(W, H)
+    prod = Calls(jpeg._lib.lib(), torch, ent, nt, d_coef)
+    prod.pack()
+    prod.pack_tight()
+    prod.n, prod.n_t = int(prod.len.item()), int(prod.len_t.item())
+    prod.unpack()
+    prod.direct()
+    prod.direct_tight()
+    torch.cuda.synchronize()
+    if args.once:
+        for _ in range(args.once):
+            prod.pack()
+            prod.pack_tight()
+            prod.direct()
+            prod.direct_tight()
+        torch.cuda.synchronize()
+        return
+    ok = prod.res3.cpu().tolist() == [prod.n, -1, 0] and prod.res3_t.cpu().tolist() == [prod.n_t, -1, 0] \
+        and bool(torch.equal(prod.coef, d_coef)) and bool(torch.equal(prod.coef_t, d_coef)) \
+        and prod.res2.cpu().tolist() == [prod.n, -1] \
+        and jpeg.stream_format(prod.out_t[:16].cpu().numpy().tobytes()) == (W, H, 1, True)
+    res = {"image": f"{name} {W}x{H}", "tiles": nt, "jpr1_bytes": prod.n, "jpt1_bytes": prod.n_t,
+           "jpr1_bytes_per_tile": round(prod.n / nt, 2), "jpt1_bytes_per_tile": round(prod.n_t / nt, 2),
+           "jpt1_over_jpr1": round(prod.n_t / prod.n, 4), "outputs_equal": ok, "steps": args.steps,
+           "rounds": args.rounds}
+    calls = [("pack", prod.pack), ("pack_tight", prod.pack_tight), ("unpack", prod.unpack),
+             ("stream_decode", prod.direct), ("stream_decode_tight", prod.direct_tight)]
+    if other is not None:
+        par = Calls(other, torch, ent, nt, d_coef)
+        par.pack()
+        par.n = int(par.len.item())
+        par.unpack()
+        par.direct()
+        torch.cuda.synchronize()
+        res["against_outputs_equal"] = par.n == prod.n and bool(torch.equal(par.out[:par.n], prod.out[:prod.n])) \
+            and bool(torch.equal(par.coef, prod.coef)) and par.res3.cpu().tolist() == prod.res3.cpu().tolist() \
+            and all(bool(torch.equal(getattr(par.back, f), getattr(prod.back, f))) for f in ("bits", "meta", "table"))
+        calls += [("against_pack", par.pack), ("against_unpack", par.unpack),
+                  ("against_stream_decode", par.direct)]
+    ms = {k: [] for k, _ in calls}
+    for r in range(args.rounds):                      # alternated; the order turns with the round
+        for key, fn in calls[r % len(calls):] + calls[:r % len(calls)]:
+            settle(fn, torch.cuda.synchronize, chunk=20)
+            ms[key].append(timed(fn, args.steps, torch))
+    for key, _ in calls:
+        res[key + "_ms"] = spread(ms[key])
+    if other is not None:
+        for key in ("pack", "unpack", "stream_decode"):
+            res[key + "_over_against"] = round(
+                res[key + "_ms"]["median"] / res["against_" + key + "_ms"]["median"], 4)
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--once", type=int, default=0)
     ap.add_argument("--decode", action="store_true")
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--tight", action="store_true")
+    ap.add_argument("--against", default=None, help="with --tight: a second liblz4jpeg.so to alternate with")
     args = ap.parse_args()
     import torch
     from lz4jpeg import jpeg, synth
@@ -189,10 +319,19 @@ def main():
         settle(lambda: d_warm.add_(1), torch.cuda.synchronize, ms=100.0, chunk=16)
         del d_warm
 
+    other = None
+    if args.against:
+        import ctypes
+        other = ctypes.CDLL(os.path.abspath(args.against), mode=ctypes.RTLD_LOCAL)
+
     for name, img in images.items():
         d_coef = jpeg.encode_device(img, W, H)
         ent = jpeg.Entropy(nt, device=dev)
         ent.encode(d_coef)
+        if args.tight:
+            torch.cuda.synchronize()
+            tight_side(args, torch, jpeg, name, ent, d_coef, other)
+            continue
         back = jpeg.Entropy(nt, device=dev)
         d_out = torch.empty(jpeg.pack_bound(W, H), dtype=torch.uint8, device=dev)
         d_len = torch.zeros(1, dtype=torch.int64, device=dev)

@@ -20,9 +20,10 @@ __global__ __launch_bounds__(64) void lz4_matches(const uint8_t *__restrict__ in
   if (lane < 16) S.buf[kInOff + n + lane] = 0;
   wave_sync();
   TileKeys K;                            // (unused: the block is staged)
+  RecBatch B;                            // (unused: no records)
   ProfClock prof = PROF_START();
   encode_block<true, false>(S, n, nullptr, K, nullptr, mout + (size_t)t * kBlk, nullptr, nullptr,
-                            nullptr, lane, prof);
+                            nullptr, lane, prof, B, true, nullptr, nullptr, 0u);
 }
 
 // find_longest_match over a block of any length n (block_encode with a

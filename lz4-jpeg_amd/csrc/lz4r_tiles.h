@@ -31,7 +31,15 @@
 //             left-maximal by its own bit
 // and the registers a block starts from (lane, the kernel arguments, m0 and
 // the priority, both set by the asm blocks that use them) do not depend on
-// the block before.  tests/test_gpu_lz4_runs.py pins it against the oracle.
+// the block before -- but for the one state that crosses blocks on purpose,
+// RecBatch: the match words of a block whose records wait for the next
+// block's (a VGPR, lanes 0..31) and the number of those lanes (an SGPR).  It
+// is safe because it lives in registers only (no block writes them but the
+// walk, which starts at lane 32 while a block waits, and is undone when it
+// runs on past lane 63), it never outlives the run (the last block of a run,
+// and any block before a staged one, leaves with its round), and a round
+// reads nothing from LDS.  tests/test_gpu_lz4_runs.py and
+// tests/test_gpu_lz4_records_batch.py pin it against the oracle.
 //
 // Per block:
 //   load     a lane's five positions need 14 dwords (TileKeys), straight from
@@ -74,7 +82,10 @@
 //            (lz4r_layout.h) -> the block's record scratch (a dense 96-B
 //            head: header and records 0..22; an overflow slot for the rest);
 //            the block's byte count -> usz (u32, for the scan) and bsizes
-//            (u16).
+//            (u16).  Two consecutive unstaged blocks of a run share one such
+//            round, one on each half of the wave (RecBatch, flush_records:
+//            a text block has ~15 sequences); a staged block, or one with
+//            more than 31 match sequences, has a round of its own.
 #pragma once
 #include <type_traits>
 
@@ -129,10 +140,126 @@ __device__ __forceinline__ void keys_arrived(TileKeys &K) {
   asm volatile("" : "+v"(K.r0), "+v"(K.r[0]), "+v"(K.r[1]), "+v"(K.r[2]), "+v"(K.r[3]));
 }
 
+// The records of two consecutive kFull blocks of a run leave in one round:
+// the first block's walk writes its match words into lanes 0.. of a register,
+// the second's into lanes 32.., and each block closes with a lane for its
+// literal-only tail (n << 19), used or not.  A block of more than 31 match
+// sequences does not fit a half and leaves alone.  The state that crosses
+// blocks is the register and one SGPR; nothing of it is in LDS.
+struct RecBatch {
+  uint32_t seqv = 0;   // lane k: the pending block's sequence k
+  uint32_t p0 = 0;     // 0: no block pending; else the lanes it takes (1 .. 32) |
+                       // (it has a truncated match) << 8 | kHalf << 16 (the lane
+                       // the next walk starts from)
+};
+constexpr int kHalf = 32;
+
+// the inclusive sums of the lanes' values within each half of the wave
+// (wave_incl_add without its last step)
+__device__ __forceinline__ uint32_t half_incl_add(uint32_t v) {
+  v += dpp<0x111, 0xf, 0xf>(v);
+  v += dpp<0x112, 0xf, 0xf>(v);
+  v += dpp<0x114, 0xf, 0xf>(v);
+  v += dpp<0x118, 0xf, 0xf>(v);
+  v += dpp<0x142, 0xa, 0xf>(v);
+  return v;
+}
+
+// Block tb + lane's header dword = hdr, usz = w, bsizes = (u16) w in the lanes
+// of m, EXEC masked once around the three stores (store_lanes1's way).  The
+// block index goes into the lanes' 32-bit offsets off the arrays' bases (a
+// launch has at most 2^24 blocks, lz4r.hip kChunk: 96 tb < 2^31); a pointer
+// per array and block cost three SALU each.
+__device__ __forceinline__ void store_block_totals(uint64_t m, uint32_t tb, int lane, uint32_t hdr,
+                                                   uint32_t w, uint8_t *heads, uint32_t *usz,
+                                                   uint16_t *bsizes) {
+  const uint32_t bl = tb + (uint32_t)lane;
+  uint64_t save;
+  asm volatile(
+      "s_and_saveexec_b64 %0, %1\n\t"
+      "global_store_dword %2, %5, %7\n\t"
+      "global_store_dword %3, %6, %8\n\t"
+      "global_store_short %4, %6, %9\n\t"
+      "s_or_b64 exec, exec, %0"
+      : "=&s"(save)
+      : "s"(m), "v"(bl * (uint32_t)kHead), "v"(bl * 4u), "v"(bl * 2u), "v"(hdr), "v"(w), "s"(heads),
+        "s"(usz), "s"(bsizes)
+      : "memory", "scc");
+}
+
+// One records round for the block on lanes [0, f0) of wv and, when f1, the
+// block after it on lanes [32, 32 + f1) (both kFull: n = kBlk); tb: the first
+// block's index in the launch's arrays.  What a block leaves is what its own
+// round left (encode_block): record k at dword 1 + k of the head below
+// kHeadW - 1 and in the overflow slot from there on, the header dword, the
+// byte count.  kFast: neither block has a truncated match.
+template <bool kFast>
+__device__ __forceinline__ void flush_records(const uint32_t wv, const uint32_t f0,
+                                              const uint32_t f1, const uint32_t tb,
+                                              uint8_t *__restrict__ heads,
+                                              uint8_t *__restrict__ ovfs,
+                                              uint32_t *__restrict__ usz,
+                                              uint16_t *__restrict__ bsizes, const int lane) {
+  constexpr int n = kBlk;
+  const int M = (int)((wv >> 9) & 255u);
+  const int end = (int)(wv >> 19);
+  const uint32_t cq = (uint32_t)(end - M);                          // the match start
+  const uint32_t upv = dpp<0x138, 0xf, 0xf>((uint32_t)end);         // wave_shr:1
+  // a block's first sequence has its literal run start at 0, not at the lane below
+  const int pend = (int)sel_mask(0x0000000100000001ull, 0u, upv);
+  const int L = (int)cq - pend;
+  // every taken lane but a tail with no literal left (a match lane has
+  // pend <= its match start < n)
+  const uint64_t am = (((1ull << f0) - 1ull) | ((1ull << f1) - 1ull) << kHalf) & ballot(pend < n);
+  uint32_t ws;                        // bytes | size field << 16 (kFast: the bytes are both)
+  if constexpr (kFast) {
+    ws = (uint32_t)(L + 5) + (L >= 15 ? 1u : 0u) + (L == 270 ? 1u : 0u) + (M >= 19 ? 1u : 0u);
+  } else {
+    ws = (uint32_t)(L + 5 + (L >= 15 ? 1 : 0) + (L == 270 ? 1 : 0)) * 0x10001u;
+    ws += M >= 19 ? 0x10001u : 0u;
+    ws += (uint32_t)(M - 1) < 3u ? 0x10000u : 0u;
+  }
+  const uint32_t sc = half_incl_add(sel_mask(am, ws, 0u));
+  // the blocks' totals stand in the last lane of their halves -> the header
+  // dword and the byte count in lane 0 (first block) and the others (second)
+  const uint32_t t0 = (uint32_t)__builtin_amdgcn_readlane((int)sc, kHalf - 1);
+  const uint32_t t1 = lane63(sc);
+  const uint32_t ns0 = (uint32_t)__popc((uint32_t)am), ns1 = (uint32_t)__popc((uint32_t)(am >> kHalf));
+  uint32_t hdr, wb;
+  if constexpr (kFast) {
+    hdr = write_lane<0>(t1 | (ns1 << 16), t0 | (ns0 << 16));
+    wb = (hdr & 0xFFFFu) + 3u;
+  } else {
+    // (opaque: as one expression the two shifts are taken for a funnel shift,
+    // which only the VALU has)
+    uint32_t z0 = t0 >> 16, z1 = t1 >> 16;
+    asm("" : "+s"(z0));
+    asm("" : "+s"(z1));
+    hdr = write_lane<0>(z1 | (ns1 << 16), z0 | (ns0 << 16));
+    wb = write_lane<0>((t1 & 0xFFFFu) + 3u, (t0 & 0xFFFFu) + 3u);
+  }
+  // record kk = lane & 31 of block lane >> 5: the head below kHeadW - 1, the
+  // overflow slot from there on (store_lanes1 adds the header's 4 bytes)
+  constexpr uint64_t kHeadLanes = ((1ull << (kHeadW - 1)) - 1ull) * 0x0000000100000001ull;
+  // (the second half's offsets by arithmetic on lane & 32: a select by a
+  // constant lane mask costs an SGPR pair the kernel does not have)
+  const uint32_t x4 = 4u * (uint32_t)lane, h32 = (uint32_t)lane & (uint32_t)kHalf;
+  store_lanes1(am & kHeadLanes, reinterpret_cast<uint32_t *>(heads + (size_t)tb * kHead),
+               x4 - h32 * ((128 - kHead) / kHalf), wv);
+  const uint64_t om = am & ~kHeadLanes;
+  if (om)
+    store_lanes1(om, reinterpret_cast<uint32_t *>(ovfs + (size_t)tb * kOvf) - kHeadW,
+                 x4 + (h32 << 3) + (h32 >> 1), wv);
+  static_assert(kOvf - 4 * kHalf == 8 * kHalf + kHalf / 2, "the second overflow slot from lane & 32");
+  store_block_totals(f1 ? 3ull : 1ull, tb, lane, hdr, wb, heads, usz, bsizes);
+}
+static_assert((128 - kHead) % kHalf == 0 && kHeadW - 1 < kHalf, "the second half's records");
+
 // Encode one block (kFull: its dwords in K, the bytes at gsrc; otherwise n
 // bytes staged at S.buf[kInOff]) as sequence records:
-// dwords 0 .. kHeadW - 1 (header, records 0..22) at head, record k >= 23 at
-// ovf[k + 1 - kHeadW]; returns the bytes its stream takes.
+// dwords 0 .. kHeadW - 1 (header, records 0..22) at its head (heads + t kHead),
+// record k >= 23 at dword k + 1 - kHeadW of its overflow slot (ovfs + t kOvf),
+// and the bytes its stream takes at usz[t] / bsizes[t].
 // kMatchesOnly: stop after the best-match scan and store every position's
 // find_longest_match result to mout instead (lz4r_block_matches_device).
 // next (kFull in a run, kTileRun > 1): the block whose dwords are loaded into K
@@ -140,14 +267,19 @@ __device__ __forceinline__ void keys_arrived(TileKeys &K) {
 // block -- the block the caller encodes next when that is a kFull block too,
 // else this block again (gsrc; never used, but the load is unconditional: no
 // branch in the index, and K has one definition per block).
+// B (kFull in a run): the block's records wait for the next block's and leave
+// in a round shared with them (flush_records) -- at once when flush_after (the
+// caller encodes no kFull block next) or when they are the second block's.
 template <bool kMatchesOnly, bool kFull>
-__device__ __forceinline__ int encode_block(TileLds &S, int n_arg, const uint8_t *__restrict__ gsrc,
+__device__ __forceinline__ void encode_block(TileLds &S, int n_arg, const uint8_t *__restrict__ gsrc,
                                             TileKeys &K, const uint8_t *__restrict__ next,
                                             uint32_t *__restrict__ mout,
-                                            uint32_t *__restrict__ head,
-                                            uint32_t *__restrict__ ovf,
+                                            uint8_t *__restrict__ heads,
+                                            uint8_t *__restrict__ ovfs,
                                             uint32_t *__restrict__ status, const int lane,
-                                            ProfClock &prof) {
+                                            ProfClock &prof, RecBatch &B, const bool flush_after,
+                                            uint32_t *__restrict__ usz,
+                                            uint16_t *__restrict__ bsizes, const uint32_t t) {
   // kFull: a whole 300-byte block of a 4-byte aligned input that is not the
   // launch's last (every block but one): n is a constant, only round 4's
   // lanes 41..63 hold positions past the last 4-gram start, and the block is
@@ -392,7 +524,7 @@ __device__ __forceinline__ int encode_block(TileLds &S, int n_arg, const uint8_t
       const int len = (int)(v[r] >> 19) - p;
       if (p < n) mout[p] = len >= 4 ? (uint32_t)len | ((v[r] & 511u) << 16) : 0u;
     }
-    return 0;
+    return;
   }
   // The scan values are end << 19 | end << 9 | dist (the lexicographic order
   // of (end, dist): the middle copy follows the end), so x = v - p << 9 =
@@ -469,33 +601,93 @@ __device__ __forceinline__ int encode_block(TileLds &S, int n_arg, const uint8_t
   // i.e. its field 4 (c + M) <= 4 n (kWordEnd's is 4 * 319 > 4 n): three VALU
   // and two SALU per sequence.
   const uint32_t lim = (uint32_t)(4 * n + 1) << 17;
-  int it = 0;
-  uint32_t seqv = 0;
+  // the walk into sq from lane l0 on; returns the lane after the last written
+  // (not reduced mod 64: past lane 63 the writes wrap)
+  auto walk_words = [&](uint32_t &sq, int l0) {
+    int l1 = l0;
+    if (w0 < lim) {
+      static_assert(kWordOff < 65536, "ds_read offset field");
+      uint32_t w = w0, va = w0 >> 17, vt;
+      asm volatile(
+          "s_mov_b32 m0, %7\n"
+          "1:\n\t"
+          "v_writelane_b32 %0, %1, m0\n\t"
+          "ds_read_b32 %3, %2 offset:%c6\n\t"
+          "s_add_u32 m0, m0, 1\n\t"
+          "s_waitcnt lgkmcnt(0)\n\t"
+          "v_readfirstlane_b32 %1, %3\n\t"
+          "v_lshrrev_b32 %2, 17, %3\n\t"
+          "s_cmp_lt_u32 %1, %5\n\t"
+          "s_cbranch_scc1 1b\n\t"
+          "s_mov_b32 %4, m0"
+          : "+v"(sq), "+s"(w), "+v"(va), "=&v"(vt), "=&s"(l1)
+          : "s"(lim), "i"(kWordOff), "s"(l0)
+          : "scc", "memory");
+    }
+    return l1;
+  };
   // The walk is the block's one serial chain: the wave issues it at raised
   // priority, so on a SIMD shared with waves in their parallel phases each
   // step goes first (-0.3 % lz4_tiles, tools/ab_inproc.py; raising the index,
   // candidate, scan or records phases instead measured 0.2-5 % slower)
-  __builtin_amdgcn_s_setprio(3);
-  if (w0 < lim) {
-    static_assert(kWordOff < 65536, "ds_read offset field");
-    uint32_t w = w0, va = w0 >> 17, vt;
-    asm volatile(
-        "s_mov_b32 m0, 0\n"
-        "1:\n\t"
-        "v_writelane_b32 %0, %1, m0\n\t"
-        "ds_read_b32 %3, %2 offset:%c6\n\t"
-        "s_add_u32 m0, m0, 1\n\t"
-        "s_waitcnt lgkmcnt(0)\n\t"
-        "v_readfirstlane_b32 %1, %3\n\t"
-        "v_lshrrev_b32 %2, 17, %3\n\t"
-        "s_cmp_lt_u32 %1, %5\n\t"
-        "s_cbranch_scc1 1b\n\t"
-        "s_mov_b32 %4, m0"
-        : "+v"(seqv), "+s"(w), "+v"(va), "=&v"(vt), "=s"(it)
-        : "s"(lim), "i"(kWordOff)
-        : "scc", "memory");
+  constexpr bool kBat = kFull && kTileRun > 1;   // the records wait in B for a shared round
+  int it;
+  uint32_t seqv;
+  if constexpr (kBat) {
+    // This block's sequences go to lanes 0.. (no block pending) or 32.. (one
+    // pending), then its tail lane.  If they do not fit the half (the walk
+    // wrote on past it -- over the pending block's words once its lane select
+    // wrapped), the register is put back, the pending block leaves alone, and
+    // the block is walked again from lane 0 and takes the one-block path below.
+    const uint32_t p0 = B.p0;
+    const int l0 = (int)(p0 >> 16);
+    const uint32_t before = B.seqv;
+    seqv = before;
+    __builtin_amdgcn_s_setprio(3);
+    const int l1 = walk_words(seqv, l0);
+    __builtin_amdgcn_s_setprio(0);
+    it = l1 - l0;
+    const bool fits = it < kHalf;     // with the tail lane
+    PROF_MARK(5);                     // walk
+    keys_arrived(K);                  // the next block's: loaded since the index
+    PROF_MARK(7);
+    // the round: of the pending block and this one, of this one (none
+    // pending), or of the pending one (this one does not fit).  Plain
+    // integers and nested branches: as bools the conditions became lane masks,
+    // two SALU each.
+    uint32_t f0 = p0 & 255u, f1 = 0u, slowm = p0 & 256u, rv = before;
+    if (fits) {
+      rv = (lane == l1) ? (uint32_t)n << 19 : seqv;
+      slowm |= fastw ? 0u : 256u;
+      if (l0 == 0) {
+        if (!flush_after) {           // waits for the next block
+          B.seqv = rv;
+          B.p0 = (uint32_t)(it + 1) | slowm | (uint32_t)kHalf << 16;
+          return;
+        }
+        f0 = (uint32_t)(it + 1);
+      } else {
+        f1 = (uint32_t)(it + 1);
+      }
+    }
+    B.p0 = 0;
+    if (f0) {
+      const uint32_t tb = t - (uint32_t)(l0 >> 5);   // the round's first block
+      if (slowm == 0u)
+        flush_records<true>(rv, f0, f1, tb, heads, ovfs, usz, bsizes, lane);
+      else
+        flush_records<false>(rv, f0, f1, tb, heads, ovfs, usz, bsizes, lane);
+    }
+    PROF_MARK(6);                     // records (of both blocks of a round)
+    if (fits) return;
+    seqv = 0;
+    walk_words(seqv, 0);              // (it stays)
+  } else {
+    seqv = 0;
+    __builtin_amdgcn_s_setprio(3);
+    it = walk_words(seqv, 0);
+    __builtin_amdgcn_s_setprio(0);
   }
-  __builtin_amdgcn_s_setprio(0);
   // Past 64 sequences (only with truncated matches) the walk is redone into S.seq.
   const bool slow = it > 64;
   int Sv_slow = 0;
@@ -510,11 +702,8 @@ __device__ __forceinline__ int encode_block(TileLds &S, int n_arg, const uint8_t
     wave_sync();
   }
   PROF_MARK(5);                       // walk
-  if (kFull && kTileRun > 1) {
-    keys_arrived(K);                  // the next block's: loaded since the index
-    PROF_MARK(7);
-  }
   // ---- sequence records: lane kk = sequence kk -----------------------------
+  // (the block alone: a staged block, or one that did not fit into the batch)
   // A round is 64 consecutive sequences; the match sequences are a prefix
   // (cpos < n), followed by the literal-only tail when the last match ends
   // before n (LZ4.c:585-612).  Rounds go on while a round is all matches.
@@ -523,6 +712,8 @@ __device__ __forceinline__ int encode_block(TileLds &S, int n_arg, const uint8_t
   // sequence k - 1's match ends; the tail is n << 19) -- after a header dword,
   // the sum of the sequences' size fields | the sequence count << 16.  lz4_emit writes the bytes
   // (write_sequence / write_block, LZ4.c:365-425) straight into the stream.
+  uint32_t *const head = reinterpret_cast<uint32_t *>(heads + (size_t)t * kHead);
+  uint32_t *const ovf = reinterpret_cast<uint32_t *>(ovfs + (size_t)t * kOvf);
   int nseq = 0;
   int ocar = 3;                      // block header: u8 nseq, u16 size
   int szsum = 0;
@@ -596,8 +787,10 @@ __device__ __forceinline__ int encode_block(TileLds &S, int n_arg, const uint8_t
       rounds(std::false_type{});
   }
   PROF_MARK(6);                       // records
-  if (lane == 0) head[0] = (uint32_t)szsum | ((uint32_t)nseq << 16);
-  return ocar;
+  // (no branch on the lane here: where it joined the batched return above,
+  // the compiler took the batch state for lane-dependent and kept it in VGPRs)
+  store_block_totals(1ull, t, lane, (uint32_t)szsum | ((uint32_t)nseq << 16), (uint32_t)ocar, heads,
+                     usz, bsizes);
 }
 
 // (8 waves per SIMD = 64 VGPRs: around a loop the compiler would otherwise
@@ -626,13 +819,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
   const uint32_t nbg = nb + (last_n >= 24 ? 1u : 0u);
   auto full = [&](uint32_t t) { return kAligned && t + 2 < nbg; };
   TileKeys K;
-  for (uint32_t t = t0; t < t1; ++t) {
+  RecBatch B;
+  // (the block's bytes by a pointer that steps, so that `in` is not kept too)
+  const uint8_t *src = in + (size_t)t0 * kBlk;
+  for (uint32_t t = t0; t < t1; ++t, src += kBlk) {
     const int lane = block_lane();
-    const int n = t == nb - 1 ? (int)last_n : kBlk;
-    const uint8_t *src = in + (size_t)t * kBlk;
-    uint32_t *const head = reinterpret_cast<uint32_t *>(heads + (size_t)t * kHead);
-    uint32_t *const ovf = reinterpret_cast<uint32_t *>(ovfs + (size_t)t * kOvf);
-    int W;
+    // (the last block, t == nb - 1, told from nbg: nb itself is not kept
+    // through the loop -- the kernel has no scalar register to spare)
+    const int n = t + 1 + (last_n >= 24 ? 1u : 0u) == nbg ? (int)last_n : kBlk;
     if (full(t)) {
       // the run's first block waits for its own loads; every other finds its
       // dwords in K, loaded during the block before (which was full too).
@@ -645,8 +839,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         PROF_MARK(7);                    // wave start .. the first block's keys are here
       }
       const bool pf = kTileRun > 1 && t + 1 < t1 && full(t + 1);
-      W = encode_block<false, true>(S, kBlk, src, K, pf ? src + kBlk : src, nullptr, head, ovf,
-                                    status, lane, prof);
+      // (not prefetched = no kFull block follows in this run: the pending
+      // records leave with this block's)
+      encode_block<false, true>(S, kBlk, src, K, pf ? src + kBlk : src, nullptr, heads, ovfs,
+                                status, lane, prof, B, !pf, usz, bsizes, t);
     } else {
       // the last block (n <= 300: nothing may be read past the input), the one
       // before a last block of < 24 bytes, or an unaligned input: staged
@@ -655,12 +851,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
       if (lane < 16) S.buf[kInOff + n + lane] = 0;
       wave_sync();
       if (t == t0) PROF_MARK(7);         // wave start .. the first block is staged
-      W = encode_block<false, false>(S, n, nullptr, K, nullptr, nullptr, head, ovf, status, lane,
-                                     prof);
-    }
-    if (lane == 0) {
-      usz[t] = (uint32_t)W;
-      bsizes[t] = (uint16_t)W;
+      encode_block<false, false>(S, n, nullptr, K, nullptr, nullptr, heads, ovfs, status, lane,
+                                 prof, B, true, usz, bsizes, t);
     }
     wave_sync();   // the next block's LDS writes stay behind this block's reads
   }

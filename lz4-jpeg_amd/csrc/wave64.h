@@ -36,6 +36,13 @@ __device__ __forceinline__ uint32_t lane63(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 
+// v with the wave-uniform s in lane kLane (v_writelane_b32, constant lane select)
+template <int kLane>
+__device__ __forceinline__ uint32_t write_lane(uint32_t v, uint32_t s) {
+  asm("v_writelane_b32 %0, %1, %2" : "+v"(v) : "s"(s), "i"(kLane));
+  return v;
+}
+
 __device__ __forceinline__ int ctz64(uint64_t m) { return __builtin_ctzll(m); }
 
 // lane mask of a predicate, straight from the compare (hip's __ballot goes

@@ -4,7 +4,9 @@ wave per block; chosen with LZ4JPEG_LIB): run the 1 GiB corpus once to warm up,
 then `reps` calls, and print the summed s_memtime cycles of each phase.
 "key wait" is the time from the wave's first instruction (a run's first
 block) or from the end of the block before (the others) until the block's
-key dwords have arrived: the cold loads, or what the prefetch left."""
+key dwords have arrived: the cold loads, or what the prefetch left.
+"emission" (the records round) is paid once for two blocks of a run, in the
+second block; the figure is still the average per block."""
 import ctypes
 import os
 import sys

@@ -277,6 +277,43 @@ int jpegr_pack_tight_device(const void *d_bits, const void *d_meta, const void *
                             void *d_out_len, void *d_scratch, void *stream);
 int jpegr_stream_format(const uint8_t header[16], int *w, int *h, int *nimg, int *format);
 
+/* Entropy encode straight to a stream, with no slots: d_coef in
+ * jpegr_encode_device's layout (16-B aligned; ntiles = nimg * ceil(w/8) *
+ * ceil(h/8)) to the bytes that jpegr_entropy_encode_device followed by
+ * jpegr_pack_device (format JPEGR_STREAM_JPR1) or jpegr_pack_tight_device
+ * (JPEGR_STREAM_JPT1) writes -- the canonical modes, the deferred streams and
+ * the clamping of a stream that overflows the reference's buffers included --
+ * from a scratch of about the stream's own size instead of 1,292 B of slots
+ * per tile.
+ * jpegr_pack_device's contract holds: asynchronous on `stream`, no host
+ * read-back, nothing kept on the host between calls (capturable in a graph, a
+ * replay re-initialises every counter itself); a u64 at d_out_len (8-B
+ * aligned): the stream length, or the exact capacity needed when that exceeds
+ * `cap`, in which case d_out[0, cap) still holds the stream's first cap bytes
+ * and nothing at or past d_out + cap is written; d_out 16-B aligned.  NULL
+ * pointers, bad dimensions, more than 2^32 tiles, a format other than the two,
+ * a misaligned d_coef, d_out, d_out_len, d_scratch (16 B) or d_result (8 B):
+ * JPEGR_ERR_ARG before any HIP call.
+ * d_result: two u64 on the device, initialised by the call itself in stream
+ * order:
+ *   [0] the length again
+ *   [1] the streams that overflow the reference's char code[32] /
+ *       sequence[1024|512] buffers (d_status[0] of the slot encoder): this
+ *       call's count, never accumulated
+ * d_scratch: jpegr_stream_encode_scratch_bytes(ntiles, cap) bytes, at most
+ * cap + 128 ntiles + 4096 and monotone in both arguments (the finished
+ * streams lie in a dense arena sized from cap, behind a directory of 24 B per
+ * tile).  Several calls may be in flight at once, each with its own scratch
+ * and result.  Whatever the coefficients say, no write leaves d_out[0, cap),
+ * the scratch and the result words.  When cap is short of the stream, the
+ * streams that the arena had no room for and that start below cap are encoded
+ * a second time, a lane each, straight to d_out; otherwise that last launch
+ * exits at once. */
+size_t jpegr_stream_encode_scratch_bytes(size_t ntiles, size_t cap);
+int jpegr_stream_encode_device(const void *d_coef, int w, int h, int nimg, int format,
+                               void *d_out, size_t cap, void *d_out_len,
+                               void *d_scratch, void *d_result, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,8 @@ SIGNATURES = [
     ("jpegr_pack_tight_device", _i, [_vp, _vp, _vp, _i, _i, _i, _vp, _c_size, _vp, _vp, _vp]),
     ("jpegr_stream_format", _i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i),
                                  ctypes.POINTER(_i)]),
+    ("jpegr_stream_encode_scratch_bytes", _c_size, [_c_size, _c_size]),
+    ("jpegr_stream_encode_device", _i, [_vp, _i, _i, _i, _i, _vp, _c_size, _vp, _vp, _vp, _vp]),
     ("jpegr_planes_device", _i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     ("jpegr_dct_blocks_device", _i, [_vp, _i, _i, _i, _vp, _vp]),
     ("jpegr_quantize_device", _i, [_vp, _vp, _i, _c_size, _vp]),

@@ -304,14 +304,80 @@ def decompress_images_device(d_stream, first=0, count=None):
     return out, w, h, count
 
 
-def compress_device(d_rgba, w, h, nimg=1, tight=False):
+def stream_encode_scratch_bytes(ntiles, cap):
+    return int(_lib.lib().jpegr_stream_encode_scratch_bytes(ntiles, cap))
+
+
+def encode_stream_device(d_coef, w, h, nimg=1, tight=False, d_out=None, d_len=None, d_result=None,
+                         scratch=None, stream=None):
+    """encode_device's coefficients straight to a JPR1 (tight=True: JPT1)
+    stream, with no slots (jpegr_stream_encode_device): the bytes of
+    Entropy.encode + pack_device.  Returns (d_out, d_len, d_result): d_out a
+    uint8 tensor (pack_bound bytes when not given), d_len one int64 holding the
+    stream length -- or the capacity needed when that exceeds d_out's size, in
+    which case nothing past d_out is written -- and d_result two int64, [0] the
+    length again, [1] the streams that overflow the reference's buffers.
+    scratch: stream_encode_scratch_bytes(ntiles, d_out.numel()) bytes.
+    Asynchronous: no read-back."""
+    import torch
+    nt = nimg * tiles(w, h)
+    if d_coef.numel() * d_coef.element_size() < nt * 256:
+        raise ValueError("d_coef smaller than ntiles * 128 int16")
+    dev = d_coef.device
+    if d_out is None:
+        d_out = torch.empty(pack_bound(w, h, nimg), dtype=torch.uint8, device=dev)
+    if d_len is None:
+        d_len = torch.zeros(1, dtype=torch.int64, device=dev)
+    if d_result is None:
+        d_result = torch.empty(2, dtype=torch.int64, device=dev)
+    need = stream_encode_scratch_bytes(nt, d_out.numel())
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif scratch.numel() < need:
+        raise ValueError("scratch smaller than stream_encode_scratch_bytes(ntiles, cap)")
+    rc = _lib.lib().jpegr_stream_encode_device(
+        ctypes.c_void_p(d_coef.data_ptr()), w, h, nimg, STREAM_JPT1 if tight else STREAM_JPR1,
+        ctypes.c_void_p(d_out.data_ptr()), d_out.numel(), ctypes.c_void_p(d_len.data_ptr()),
+        ctypes.c_void_p(scratch.data_ptr()), ctypes.c_void_p(d_result.data_ptr()),
+        _stream_handle(stream))
+    if rc != 0:
+        raise JpegError(rc, "jpegr_stream_encode_device")
+    return d_out, d_len, d_result
+
+
+def encode_stream_exact_device(d_coef, w, h, nimg=1, tight=False, cap=None):
+    """(a uint8 tensor of exactly the stream, the overflow count) by
+    encode_stream_device into `cap` bytes -- by default a quarter of the bound,
+    which holds every stream measured so far (a random 4K image takes 150 B a
+    tile of the bound's 1,038) -- and, when the stream is longer, once more
+    into exactly what the first call asked for.  Reads the result back."""
+    import torch
+    if cap is None:
+        cap = 16 + nimg * tiles(w, h) * 258
+    d_out = torch.empty(cap, dtype=torch.uint8, device=d_coef.device)
+    _, _, d_result = encode_stream_device(d_coef, w, h, nimg, tight=tight, d_out=d_out)
+    n, over = d_result.cpu().tolist()
+    if n > cap:
+        d_out = torch.empty(n, dtype=torch.uint8, device=d_coef.device)
+        _, _, d_result = encode_stream_device(d_coef, w, h, nimg, tight=tight, d_out=d_out)
+        n, over = d_result.cpu().tolist()
+    return d_out[:n].clone(), over
+
+
+def compress_device(d_rgba, w, h, nimg=1, tight=False, direct=False):
     """RGBA8 images -> a uint8 tensor of exactly the JPR stream (JPR1, or JPT1
     with tight=True: the same content in fewer bytes, read by
     decompress_images_device and decode_stream_device only): encode, entropy
     encode, pack; the length is read back once, then the encoder's
     status word.  Raises JpegError if a stream overflowed the reference's
-    buffers (status[0] != 0)."""
+    buffers (status[0] != 0).  direct=True: the same bytes by
+    encode_stream_device, with no slots (d_result[1] is the status word)."""
     d_coef = encode_device(d_rgba, w, h, nimg)
+    if direct:
+        d_out, over = encode_stream_exact_device(d_coef, w, h, nimg, tight=tight)
+        if over != 0:
+            raise JpegError(-1, "compress_device: a stream overflows the reference's buffers")
+        return d_out
     ent = Entropy(nimg * tiles(w, h), device=d_rgba.device)
     ent.encode(d_coef)
     d_out, d_len = pack_device(ent, w, h, nimg, tight=tight)

@@ -4,7 +4,8 @@ jpeg.compress_device on an MI355X; bench.py's discipline: a clock pre-warm,
 settle() on each measured call, then event-timed means over back-to-back
 launches.
 
-    python tools/jpeg_pack_bench.py [--steps K] [--once N] [--decode | --tight [--against LIB]]
+    python tools/jpeg_pack_bench.py [--steps K] [--once N]
+                                    [--decode | --tight [--against LIB] | --direct [--against LIB]]
 
 Images: bench.py's 3840x2160 random image (synth.rand_rgba_device, seed 1)
 and a 3840x2160 smooth one (tests/test_gpu_entropy.py's generator).  Prints
@@ -33,7 +34,17 @@ the entropy stage was given).  --against LIB adds the JPR1 calls -- pack,
 unpack, direct decode -- of a second build of the library (the parent
 commit's, loaded beside the product's with RTLD_LOCAL) to the same rounds, and
 prints each pair with the ratio of the medians.  With --once N: N launches of
-the two packs and the two direct decodes per image and nothing else."""
+the two packs and the two direct decodes per image and nothing else.
+
+--direct: the encode straight to a stream (jpegr_stream_encode_device), both
+formats, for profiles/jpr_stream_encode.log: beside entropy encode + pack and
+entropy encode + tight pack, the stages it replaces, alternated over --rounds
+rounds in this run after the same pre-warm and settle; every output checked
+against the two-stage stream.  --against LIB adds the second build's entropy
+encode / decode, both packs and the direct decode to the same rounds, with the
+ratio of the medians per pair.  Then the device memory compress_device peaks
+at, direct or not, for one image and for eight.  With --once N: N direct
+encodes of each format per image and nothing else."""
 import argparse
 import json
 import os
@@ -293,6 +304,184 @@ def tight_side(args, torch, jpeg, name, ent, d_coef, other):
     print(json.dumps(res), flush=True)
 
 
+class EncCalls:
+    """The encode-side calls of one build of the library on one image's
+    coefficients, each with buffers of its own."""
+
+    def __init__(self, lib, torch, nt, d_coef, jpeg):
+        import ctypes
+        from lz4jpeg import _lib
+        self.lib, self.nt, self.c, self.d_coef = lib, nt, ctypes, d_coef
+        for fname, res, argt in _lib.SIGNATURES:
+            if fname.startswith("jpegr_") and hasattr(lib, fname):
+                fn = getattr(lib, fname)
+                fn.restype, fn.argtypes = res, argt
+        dev = d_coef.device
+        self.st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        self.ent = jpeg.Entropy(nt, device=dev)
+        bound = int(lib.jpegr_pack_bound(W, H, 1))
+        nscr = int(lib.jpegr_pack_scratch_bytes(nt))
+        self.out = {k: torch.empty(bound, dtype=torch.uint8, device=dev) for k in ("r", "t", "dr", "dt")}
+        self.len = {k: torch.zeros(1, dtype=torch.int64, device=dev) for k in ("r", "t", "dr", "dt")}
+        self.scr = {k: torch.empty(nscr, dtype=torch.uint8, device=dev) for k in ("r", "t", "dec")}
+        self.res3 = torch.zeros(3, dtype=torch.int64, device=dev)
+        self.coef = torch.empty_like(d_coef)
+        self.coef2 = torch.empty_like(d_coef)
+        self.n = 0
+        if hasattr(lib, "jpegr_stream_encode_device"):
+            self.enc_scratch_bytes = int(lib.jpegr_stream_encode_scratch_bytes(nt, bound))
+            self.escr = {k: torch.empty(self.enc_scratch_bytes, dtype=torch.uint8, device=dev)
+                         for k in ("dr", "dt")}
+            self.eres = {k: torch.zeros(2, dtype=torch.int64, device=dev) for k in ("dr", "dt")}
+
+    def _p(self, t):
+        return self.c.c_void_p(t.data_ptr())
+
+    def entropy_encode(self):
+        e = self.ent
+        rc = self.lib.jpegr_entropy_encode_device(self._p(self.d_coef), self.nt, self._p(e.bits),
+                                                  self._p(e.meta), self._p(e.table), self._p(e.scratch),
+                                                  self._p(e.status), self.st)
+        assert rc == 0, rc
+
+    def entropy_decode(self):
+        e = self.ent
+        rc = self.lib.jpegr_entropy_decode_device(self._p(e.bits), self._p(e.meta), self._p(e.table),
+                                                  self.nt, self._p(self.coef2), self._p(e.status), self.st)
+        assert rc == 0, rc
+
+    def _pack(self, fn, k):
+        e = self.ent
+        rc = fn(self._p(e.bits), self._p(e.meta), self._p(e.table), W, H, 1, self._p(self.out[k]),
+                self.out[k].numel(), self._p(self.len[k]), self._p(self.scr[k]), self.st)
+        assert rc == 0, rc
+
+    def pack(self):
+        self._pack(self.lib.jpegr_pack_device, "r")
+
+    def pack_tight(self):
+        self._pack(self.lib.jpegr_pack_tight_device, "t")
+
+    def two_stage(self):
+        self.entropy_encode()
+        self.pack()
+
+    def two_stage_tight(self):
+        self.entropy_encode()
+        self.pack_tight()
+
+    def _direct(self, k, fmt):
+        rc = self.lib.jpegr_stream_encode_device(self._p(self.d_coef), W, H, 1, fmt, self._p(self.out[k]),
+                                                 self.out[k].numel(), self._p(self.len[k]),
+                                                 self._p(self.escr[k]), self._p(self.eres[k]), self.st)
+        assert rc == 0, rc
+
+    def direct(self):
+        self._direct("dr", 1)
+
+    def direct_tight(self):
+        self._direct("dt", 2)
+
+    def stream_decode(self):
+        rc = self.lib.jpegr_stream_decode_device(self._p(self.out["r"]), self.n, W, H, 1, 0, self.nt,
+                                                 self._p(self.coef), self._p(self.scr["dec"]),
+                                                 self._p(self.res3), self.st)
+        assert rc == 0, rc
+
+
+def peak_bytes(torch, fn):
+    """Device bytes fn allocates at its peak, over what is allocated before it."""
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    out = fn()
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated() - base
+    del out
+    return peak
+
+
+def direct_side(args, torch, jpeg, name, img, d_coef, other):
+    """The direct encode, both formats, beside entropy encode + pack / tight
+    pack, and the existing calls of `other` (a second build's ctypes handle, or
+    None) beside this build's: same run, alternated."""
+    nt = jpeg.tiles(W, H)
+    prod = EncCalls(jpeg._lib.lib(), torch, nt, d_coef, jpeg)
+    prod.two_stage()
+    prod.pack_tight()
+    prod.direct()
+    prod.direct_tight()
+    torch.cuda.synchronize()
+    if args.once:
+        for _ in range(args.once):
+            prod.direct()
+            prod.direct_tight()
+        torch.cuda.synchronize()
+        return
+    n = {k: int(v.item()) for k, v in prod.len.items()}
+    prod.n = n["r"]
+    prod.stream_decode()
+    prod.entropy_decode()
+    torch.cuda.synchronize()
+    ok = n["dr"] == n["r"] and n["dt"] == n["t"] \
+        and bool(torch.equal(prod.out["dr"][:n["r"]], prod.out["r"][:n["r"]])) \
+        and bool(torch.equal(prod.out["dt"][:n["t"]], prod.out["t"][:n["t"]])) \
+        and prod.eres["dr"].cpu().tolist() == [n["r"], 0] and prod.eres["dt"].cpu().tolist() == [n["t"], 0] \
+        and bool(torch.equal(prod.coef, d_coef)) and bool(torch.equal(prod.coef2, d_coef))
+    res = {"image": f"{name} {W}x{H}", "tiles": nt, "jpr1_bytes": n["r"], "jpt1_bytes": n["t"],
+           "outputs_equal": ok, "steps": args.steps, "rounds": args.rounds,
+           "slot_bytes": 1292 * nt, "stream_encode_scratch_bytes_at_bound": prod.enc_scratch_bytes,
+           "stream_encode_scratch_bytes_at_stream": int(
+               prod.lib.jpegr_stream_encode_scratch_bytes(nt, n["r"]))}
+    calls = [("entropy_encode", prod.entropy_encode), ("pack", prod.pack), ("pack_tight", prod.pack_tight),
+             ("two_stage", prod.two_stage), ("two_stage_tight", prod.two_stage_tight),
+             ("stream_encode", prod.direct), ("stream_encode_tight", prod.direct_tight),
+             ("entropy_decode", prod.entropy_decode), ("stream_decode", prod.stream_decode)]
+    shared = ("entropy_encode", "pack", "pack_tight", "entropy_decode", "stream_decode")
+    if other is not None:
+        par = EncCalls(other, torch, nt, d_coef, jpeg)
+        par.two_stage()
+        par.pack_tight()
+        torch.cuda.synchronize()
+        par.n = int(par.len["r"].item())
+        par.stream_decode()
+        par.entropy_decode()
+        torch.cuda.synchronize()
+        res["against_outputs_equal"] = par.n == n["r"] and int(par.len["t"].item()) == n["t"] \
+            and bool(torch.equal(par.out["r"][:par.n], prod.out["r"][:par.n])) \
+            and bool(torch.equal(par.out["t"][:n["t"]], prod.out["t"][:n["t"]])) \
+            and bool(torch.equal(par.coef, d_coef)) and bool(torch.equal(par.coef2, d_coef))
+        calls += [("against_" + k, getattr(par, k)) for k in shared]
+    ms = {k: [] for k, _ in calls}
+    for r in range(args.rounds):                      # alternated; the order turns with the round
+        for key, fn in calls[r % len(calls):] + calls[:r % len(calls)]:
+            settle(fn, torch.cuda.synchronize, chunk=20)
+            ms[key].append(timed(fn, args.steps, torch))
+    for key, _ in calls:
+        res[key + "_ms"] = spread(ms[key])
+    med = lambda k: res[k + "_ms"]["median"]
+    res["stream_encode_over_two_stage"] = round(med("stream_encode") / med("two_stage"), 4)
+    res["stream_encode_tight_over_two_stage_tight"] = round(
+        med("stream_encode_tight") / med("two_stage_tight"), 4)
+    if other is not None:
+        for key in shared:
+            res[key + "_over_against"] = round(med(key) / med("against_" + key), 4)
+    print(json.dumps(res), flush=True)
+    if name != "random":
+        return
+    mem = {"image": f"random {W}x{H}", "what": "peak device bytes of compress_device over its input"}
+    for k in (1, 8):
+        imgs = img.repeat(k)
+        for tight in (False, True):
+            for direct in (False, True):
+                key = f"x{k}_{'jpt1' if tight else 'jpr1'}_{'direct' if direct else 'slots'}"
+                mem[key] = peak_bytes(
+                    torch, lambda: jpeg.compress_device(imgs, W, H, k, tight=tight, direct=direct))
+        del imgs
+    print(json.dumps(mem), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=200)
@@ -300,7 +489,9 @@ def main():
     ap.add_argument("--decode", action="store_true")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--tight", action="store_true")
-    ap.add_argument("--against", default=None, help="with --tight: a second liblz4jpeg.so to alternate with")
+    ap.add_argument("--direct", action="store_true")
+    ap.add_argument("--against", default=None,
+                    help="with --tight or --direct: a second liblz4jpeg.so to alternate with")
     args = ap.parse_args()
     import torch
     from lz4jpeg import jpeg, synth
@@ -326,6 +517,10 @@ def main():
 
     for name, img in images.items():
         d_coef = jpeg.encode_device(img, W, H)
+        if args.direct:
+            torch.cuda.synchronize()
+            direct_side(args, torch, jpeg, name, img, d_coef, other)
+            continue
         ent = jpeg.Entropy(nt, device=dev)
         ent.encode(d_coef)
         if args.tight:

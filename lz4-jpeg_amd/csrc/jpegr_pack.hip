@@ -1,19 +1,36 @@
-// jpegr_pack.hip -- the JPR stream: the entropy stage's fixed slots (256 B of
-// bits, 3 meta words, 256 table words per tile) packed into one byte stream
-// of variable-length tile records behind a u16 size index, and the inverse
-// (format: include/jpegr.h).
+// jpegr_pack.hip -- the JPR stream from and to slots: the entropy stage's fixed
+// slots (256 B of bits, 3 meta words, 256 table words per tile) packed into one
+// byte stream of variable-length tile records behind a u16 size index, in
+// either format, and the inverse for JPR1 (format: include/jpegr.h).  A JPT1
+// stream is JPR1's header, index and record order with each stream's table in
+// the tightest of three codings:
+//   mode 0  ncodes x { i16 value, u8 length }             (JPR1's entries)
+//   mode 1  ceil(ncodes / 2) bytes of nibble lengths, ncodes x i8 value
+//   mode 2  ceil(ncodes / 2) bytes of nibble lengths, ncodes x i16 value
+// The writer's mode is canonical (table_mode): 1 when ncodes > 0, every length
+// <= 15 and every value fits an i8; else 2 when ncodes > 0 and every length
+// <= 15; else 0.
 //
-//   pack    jpr_pack_sizes   a lane per tile: record size -> u32 (scan input)
-//                            and the stream's u16 index; the 16-B header
+//   pack    jpr_pack_sizes   JPR1.  A lane per tile: record size -> u32 (scan
+//                            input) and the stream's u16 index; the 16-B header
+//           jpt_pack_sizes   JPT1: the sizes depend on the tables.  A workgroup
+//                            per 16 tiles, a wave per 4: entry k of a stream on
+//                            lane k (the emit pass's lanes), each stream's mode
+//                            from two ballots, then as jpr_pack_sizes
 //           lz4_scan_reduce / lz4_scan_partials (lz4r_scan.h, as they are):
 //                            groups of 64 tiles, partials of 4,096; the end
 //                            of the scan is the stream length
-//           jpr_pack_emit    a workgroup per 16 tiles: records into an LDS
-//                            image of its output range, out as 16-B stores
+//           jpr_pack_emit<kTight>  a workgroup per 16 tiles: records into an
+//                            LDS image of its output range, out as 16-B stores.
+//                            JPT1: the modes are not stored, the kernel ballots
+//                            them again from the table words it loads anyway
 //   unpack  jpr_unpack_sizes index -> u32 sizes, header verdict
 //           the same scan    -> the length the header and index imply
 //           jpr_unpack_tiles a workgroup per 16 tiles: its input range
 //                            through LDS, records checked and scattered
+// One emit kernel serves both formats: with kTight == false every mode is the
+// constant 0 and what is left is the JPR1 kernel.  The format's
+// pieces, the run and the image's flush are jpegr_pack_common.h's.
 // No host-side state, no host read-back: every call can be captured in a graph.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,28 +40,6 @@
 
 namespace {
 
-// tiles per workgroup (a quarter of a scan group).  The LDS image is sized for
-// the worst case, 1,036 B a tile, so the run sets the occupancy: 16 tiles
-// (16.6 KB, 8 workgroups per CU) pack a 4K image in 0.035 ms, 32 tiles in
-// 0.051 ms, 8 tiles in 0.043 ms
-constexpr int kRun = 16;
-constexpr int kSplit = kGT / kRun;          // workgroups per scan group
-constexpr int kPW = 4;                      // waves per workgroup
-constexpr int kTW = kRun / kPW;             // tiles per wave
-constexpr int kImg = kRun * kRecMax + 16;   // the range + its lead inside a 16-B chunk
-static_assert(kGT % kRun == 0 && kRun % kPW == 0 && kImg % 16 == 0, "whole workgroups per scan group");
-
-// a channel's first byte of the bits slot, first entry of the table slot
-__device__ __forceinline__ uint32_t slot_off(int c) { return c == 0 ? 0u : c == 1 ? 128u : 192u; }
-
-// what pack copies of a stream: its codes and bit bytes, clamped to the slot
-// (a meta word past its slot cannot make any kernel here leave the slot)
-__device__ __forceinline__ uint32_t meta_codes(uint32_t m, int c) { return min(m >> 24, slot_codes(c)); }
-__device__ __forceinline__ uint32_t meta_bits(uint32_t m, int c) { return min(m & 0xFFFFu, slot_bits(c)); }
-__device__ __forceinline__ uint32_t stream_bytes(uint32_t m, int c) {
-  return 4u + 3u * meta_codes(m, c) + ((meta_bits(m, c) + 7u) >> 3);
-}
-
 __global__ __launch_bounds__(256) void jpr_pack_sizes(const uint32_t *__restrict__ meta,
                                                       size_t ntiles, size_t t_base,
                                                       uint32_t *__restrict__ tsz,
@@ -52,18 +47,71 @@ __global__ __launch_bounds__(256) void jpr_pack_sizes(const uint32_t *__restrict
                                                       uint32_t w, uint32_t h, uint32_t nimg) {
   const size_t t = t_base + (size_t)blockIdx.x * 256 + threadIdx.x;
   if (t >= ntiles) return;
-  const uint32_t sz = stream_bytes(meta[3 * t], 0) + stream_bytes(meta[3 * t + 1], 1) +
-                      stream_bytes(meta[3 * t + 2], 2);
+  const uint32_t sz = stream_bytes(meta[3 * t], 0, 0u) + stream_bytes(meta[3 * t + 1], 1, 0u) +
+                      stream_bytes(meta[3 * t + 2], 2, 0u);
   tsz[t] = sz;
-  const uint64_t pos = kHdr + 2 * (uint64_t)t;          // 2-B aligned: out is 16-B aligned
-  if (pos + 2 <= cap)
-    *reinterpret_cast<uint16_t *>(out + pos) = (uint16_t)sz;
-  else if (pos < cap)
-    out[pos] = (uint8_t)sz;
-  if (t == 0) {
-    const uint32_t hw[4] = {0x3152504Au /* "JPR1" */, w, h, nimg};
-    for (uint32_t i = 0; i < (uint32_t)kHdr && i < cap; ++i) out[i] = (uint8_t)(hw[i >> 2] >> (8 * (i & 3)));
+  put_index(out, cap, t, sz);
+  if (t == 0) put_header(out, cap, kMagicJPR1, w, h, nimg);
+}
+
+// the canonical modes of a tile's three streams from the wave's table words
+// (tb[0], tb[1]: Y entries lane, 64 + lane; tb[2]: Cr; tb[3]: Cb), as
+// Y | Cr << 2 | Cb << 4.  Wave-uniform.
+__device__ __forceinline__ uint32_t tile_modes(const uint32_t (&tb)[4], uint32_t n0, uint32_t n1,
+                                               uint32_t n2) {
+  const bool l0 = __ballot(long_len(tb[0]) || long_len(tb[1])) != 0;
+  const bool w0 = __ballot(wide_val(tb[0]) || wide_val(tb[1])) != 0;
+  const bool l1 = __ballot(long_len(tb[2])) != 0, w1 = __ballot(wide_val(tb[2])) != 0;
+  const bool l2 = __ballot(long_len(tb[3])) != 0, w2 = __ballot(wide_val(tb[3])) != 0;
+  return table_mode(n0, l0, w0) | table_mode(n1, l1, w1) << 2 | table_mode(n2, l2, w2) << 4;
+}
+
+// the live table words of a tile on this lane (0 where not live)
+__device__ __forceinline__ void load_table(const uint32_t *__restrict__ tw, int lane, uint32_t n0,
+                                           uint32_t n1, uint32_t n2, uint32_t (&tb)[4]) {
+  if ((uint32_t)lane < n0) tb[0] = tw[lane];
+  if ((uint32_t)lane + 64u < n0) tb[1] = tw[64 + lane];
+  if ((uint32_t)lane < n1) tb[2] = tw[128 + lane];
+  if ((uint32_t)lane < n2) tb[3] = tw[192 + lane];
+}
+
+__global__ __launch_bounds__(64 * kPW) void jpt_pack_sizes(
+    const uint32_t *__restrict__ meta, const uint32_t *__restrict__ table, size_t ntiles,
+    size_t wg_base, uint32_t *__restrict__ tsz, uint8_t *__restrict__ out, uint64_t cap, uint32_t w,
+    uint32_t h, uint32_t nimg) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const size_t t0 = (wg_base + blockIdx.x) * kRun;
+  if (t0 >= ntiles) return;
+  const int ntl = (int)min((size_t)kRun, ntiles - t0);
+  uint32_t tb[kTW][4], m[kTW][3];
+#pragma unroll
+  for (int i = 0; i < kTW; ++i) {                       // all 16 table loads before the first ballot
+    const int j = kTW * wv + i;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) tb[i][q] = 0u;
+    m[i][0] = m[i][1] = m[i][2] = 0u;
+    if (j < ntl) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) m[i][c] = meta[3 * (t0 + j) + c];
+      load_table(table + (t0 + j) * 256, lane, meta_codes(m[i][0], 0), meta_codes(m[i][1], 1),
+                 meta_codes(m[i][2], 2), tb[i]);
+    }
   }
+#pragma unroll
+  for (int i = 0; i < kTW; ++i) {
+    const int j = kTW * wv + i;
+    if (j >= ntl) continue;
+    const uint32_t md = tile_modes(tb[i], meta_codes(m[i][0], 0), meta_codes(m[i][1], 1),
+                                   meta_codes(m[i][2], 2));
+    if (lane == 0) {
+      const size_t t = t0 + j;
+      const uint32_t sz = stream_bytes(m[i][0], 0, md & 3u) + stream_bytes(m[i][1], 1, (md >> 2) & 3u) +
+                          stream_bytes(m[i][2], 2, md >> 4);
+      tsz[t] = sz;
+      put_index(out, cap, t, sz);
+    }
+  }
+  if (t0 == 0 && tid == 0) put_header(out, cap, kMagicJPT1, w, h, nimg);
 }
 
 // A workgroup's 16 tiles -> stream bytes [G0, G1).  Wave v takes tiles
@@ -71,8 +119,14 @@ __global__ __launch_bounds__(256) void jpr_pack_sizes(const uint32_t *__restrict
 // words lane, 64 + lane (Y), 128 + lane (Cr), 192 + lane (Cb) and dword
 // `lane` of the 256 bit bytes -- loaded only where live, all 20 issued
 // before the first is used.  Every byte of the range is written once (the
-// records are dense), so the image needs no zeroing and byte stores to LDS
-// need no atomics.
+// records are dense), by byte stores, so the image needs no zeroing and byte
+// stores to LDS need no atomics.
+// JPT1 writes the table by mode.  Entry k of a stream is on lane k of one
+// register, so the pair (2 j, 2 j + 1) of a length byte never straddles two
+// registers: lane 2 j takes lane 2 j + 1's word by one cross-lane move and
+// writes the byte; with an odd ncodes the last pair's upper lane is not live
+// and holds 0.
+template <bool kTight>
 __global__ __launch_bounds__(64 * kPW) void jpr_pack_emit(
     const uint8_t *__restrict__ bits, const uint32_t *__restrict__ meta,
     const uint32_t *__restrict__ table, size_t ntiles, size_t wg_base,
@@ -82,12 +136,8 @@ __global__ __launch_bounds__(64 * kPW) void jpr_pack_emit(
   __shared__ alignas(16) uint8_t img[kImg];
   __shared__ uint32_t smeta[kRun * 3];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const size_t wg = wg_base + blockIdx.x;
-  const size_t g = wg / kSplit;
-  const int h0 = (int)(wg % kSplit) * kRun;
-  const size_t t0 = g * kGT + h0;                       // the workgroup's first tile
+  const auto [g, t0, h0, ntl] = run_of(wg_base + blockIdx.x, ntiles);
   if (t0 >= ntiles) return;
-  const int ntl = (int)min((size_t)kRun, ntiles - t0);
   group_offsets(tid, g, ntiles, tsz, gsum, part, toff);
   if (tid < 3 * ntl) smeta[tid] = meta[3 * t0 + tid];
   __syncthreads();
@@ -105,12 +155,8 @@ __global__ __launch_bounds__(64 * kPW) void jpr_pack_emit(
     bt[i] = 0u;
     if (j < ntl) {
       const uint32_t m0 = smeta[3 * j], m1 = smeta[3 * j + 1], m2 = smeta[3 * j + 2];
-      const uint32_t *tw = table + (t0 + j) * 256;
-      const uint32_t n0 = meta_codes(m0, 0), n1 = meta_codes(m1, 1), n2 = meta_codes(m2, 2);
-      if ((uint32_t)lane < n0) tb[i][0] = tw[lane];
-      if ((uint32_t)lane + 64u < n0) tb[i][1] = tw[64 + lane];
-      if ((uint32_t)lane < n1) tb[i][2] = tw[128 + lane];
-      if ((uint32_t)lane < n2) tb[i][3] = tw[192 + lane];
+      load_table(table + (t0 + j) * 256, lane, meta_codes(m0, 0), meta_codes(m1, 1),
+                 meta_codes(m2, 2), tb[i]);
       const uint32_t mb = bc == 0 ? m0 : bc == 1 ? m1 : m2;
       if (blocal < ((meta_bits(mb, bc) + 7u) >> 3))
         bt[i] = reinterpret_cast<const uint32_t *>(bits + (t0 + j) * 256)[lane];
@@ -121,54 +167,59 @@ __global__ __launch_bounds__(64 * kPW) void jpr_pack_emit(
     const int j = kTW * wv + i;
     if (j >= ntl) continue;
     const uint32_t m[3] = {smeta[3 * j], smeta[3 * j + 1], smeta[3 * j + 2]};
+    uint32_t mds = 0u;
+    if constexpr (kTight)
+      mds = tile_modes(tb[i], meta_codes(m[0], 0), meta_codes(m[1], 1), meta_codes(m[2], 2));
+    const uint32_t md[3] = {mds & 3u, (mds >> 2) & 3u, mds >> 4};
     uint32_t o[3];                                      // each stream's first image byte
     o[0] = lead + (uint32_t)(toff[h0 + j] - G0);
-    o[1] = o[0] + stream_bytes(m[0], 0);
-    o[2] = o[1] + stream_bytes(m[1], 1);
-    if (lane < 12) {                                    // u8 rle_len | u8 ncodes | u16 nbits
+    o[1] = o[0] + stream_bytes(m[0], 0, md[0]);
+    o[2] = o[1] + stream_bytes(m[1], 1, md[1]);
+    if (lane < 12) {                                    // the stream's header, a byte per lane
       const int c = lane >> 2;
       const uint32_t mc = c == 0 ? m[0] : c == 1 ? m[1] : m[2];
       const uint32_t oc = c == 0 ? o[0] : c == 1 ? o[1] : o[2];
-      const uint32_t hw = ((mc >> 16) & 255u) | meta_codes(mc, c) << 8 | meta_bits(mc, c) << 16;
+      const uint32_t dc = c == 0 ? md[0] : c == 1 ? md[1] : md[2];
+      const uint32_t hw = stream_header((mc >> 16) & 255u, meta_codes(mc, c), meta_bits(mc, c), dc);
       img[oc + (lane & 3)] = (uint8_t)(hw >> (8 * (lane & 3)));
     }
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {                       // i16 value, u8 code length
+    for (int q = 0; q < 4; ++q) {
       const int c = q < 2 ? 0 : q - 1;
       const uint32_t k = (uint32_t)lane + (q == 1 ? 64u : 0u);
-      if (k < meta_codes(m[c], c)) {
-        uint8_t *p = img + o[c] + 4u + 3u * k;
-        const uint32_t e = tb[i][q];
-        p[0] = (uint8_t)e;
-        p[1] = (uint8_t)(e >> 8);
-        p[2] = (uint8_t)(e >> 16);
+      const uint32_t e = tb[i][q];
+      const uint32_t up = __shfl_down(e, 1);            // lane + 1's word, by every lane of the wave
+      const uint32_t nc = meta_codes(m[c], c);
+      if (k < nc) {
+        uint8_t *p = img + o[c] + 4u;
+        if (md[c] == 0) {                               // i16 value, u8 code length
+          p += 3u * k;
+          p[0] = (uint8_t)e;
+          p[1] = (uint8_t)(e >> 8);
+          p[2] = (uint8_t)(e >> 16);
+        } else {
+          if ((k & 1u) == 0) p[k >> 1] = (uint8_t)(((e >> 16) & 15u) | ((up >> 16) & 15u) << 4);
+          p += (nc + 1u) >> 1;
+          if (md[c] == 1) {
+            p[k] = (uint8_t)e;
+          } else {
+            p[2u * k] = (uint8_t)e;
+            p[2u * k + 1] = (uint8_t)(e >> 8);
+          }
+        }
       }
     }
     const uint32_t mb = bc == 0 ? m[0] : bc == 1 ? m[1] : m[2];
     const uint32_t ob = bc == 0 ? o[0] : bc == 1 ? o[1] : o[2];
+    const uint32_t db = bc == 0 ? md[0] : bc == 1 ? md[1] : md[2];
     const uint32_t nby = (meta_bits(mb, bc) + 7u) >> 3;
-    uint8_t *p = img + ob + 4u + 3u * meta_codes(mb, bc) + blocal;
+    uint8_t *p = img + ob + 4u + table_bytes(meta_codes(mb, bc), db) + blocal;
 #pragma unroll
     for (uint32_t b = 0; b < 4; ++b)
       if (blocal + b < nby) p[b] = (uint8_t)(bt[i] >> (8 * b));
   }
   __syncthreads();
-  // ---- LDS image -> stream: aligned 16-B stores; the first and last partial
-  // chunks, which neighbouring workgroups share, a byte per lane; nothing at
-  // or past cap
-  const uint64_t E = min(G1, cap);
-  if (E <= G0) return;
-  uint8_t *const outF = out + (G0 - lead);              // 16-B aligned
-  const uint32_t nrel = (uint32_t)(E - G0) + lead;
-  const uint32_t c0 = lead ? 1u : 0u, c1 = nrel >> 4;   // the whole chunks: [c0, c1)
-  for (uint32_t ci = c0 + (uint32_t)tid; ci < c1; ci += 64 * kPW)
-    __builtin_nontemporal_store(reinterpret_cast<const u32x4 *>(img)[ci],
-                                reinterpret_cast<u32x4 *>(outF + 16u * ci));
-  if (wv == kPW - 1 && lane < 32) {
-    const uint32_t x = lane < 16 ? (uint32_t)lane : 16u * c1 + (uint32_t)(lane - 16);
-    const bool own = lane < 16 ? (c0 && x >= lead && x < nrel) : (c1 >= c0 && x < nrel);
-    if (own) outF[x] = img[x];
-  }
+  image_out(img, tid, lane, wv, G0, G1, lead, out, cap);
 }
 
 // ---- unpack ---------------------------------------------------------------------
@@ -180,26 +231,17 @@ __global__ __launch_bounds__(256) void jpr_unpack_sizes(const uint8_t *__restric
                                                         uint64_t *__restrict__ result) {
   const size_t t = t_base + (size_t)blockIdx.x * 256 + threadIdx.x;
   if (t >= ntiles) return;
-  const uint64_t pos = kHdr + 2 * (uint64_t)t;
-  const uint32_t lo = pos < in_len ? in[pos] : 0u, hi = pos + 1 < in_len ? in[pos + 1] : 0u;
-  tsz[t] = lo | hi << 8;
-  if (t == 0) {
-    const uint32_t want[4] = {0x3152504Au, w, h, nimg};
-    bool ok = in_len >= kHdr + 2 * (uint64_t)ntiles;
-    for (uint32_t i = 0; ok && i < (uint32_t)kHdr; ++i)
-      ok = in[i] == (uint8_t)(want[i >> 2] >> (8 * (i & 3)));
-    result[1] = ok ? ~0ull : 0ull;
-  }
+  tsz[t] = get_index(in, in_len, t);
+  if (t == 0) result[1] = header_ok(in, in_len, ntiles, w, h, nimg, false) ? ~0ull : 0ull;
 }
 
 // A workgroup's 16 records: its input range staged in LDS (16-B loads; the
 // partial chunks at either end bytewise, so no read leaves [0, in_len)), a
-// lane per tile checks the three stream headers against the slots and the
-// indexed size, then wave v scatters tiles 4 v .. 4 v + 3: table words and
-// bit dwords rebuilt from the record's bytes, lanes as in jpr_pack_emit.  An
-// index entry over 1,036 B is malformed by itself; the window holds 16
-// records of that size, and a (well-formed) record behind such an entry is
-// read from the stream directly.
+// lane per tile checks its record (record_rule), then wave v scatters tiles
+// 4 v .. 4 v + 3: table words and bit dwords rebuilt from the record's bytes,
+// lanes as in jpr_pack_emit.  The window holds 16 records of the largest
+// well-formed size, and a (well-formed) record behind an index entry over
+// that is read from the stream directly.
 __global__ __launch_bounds__(64 * kPW) void jpr_unpack_tiles(
     const uint8_t *__restrict__ in, uint64_t in_len, size_t ntiles, size_t wg_base,
     const uint32_t *__restrict__ tsz, const uint32_t *__restrict__ gsum,
@@ -210,12 +252,8 @@ __global__ __launch_bounds__(64 * kPW) void jpr_unpack_tiles(
   __shared__ uint32_t smeta[kRun * 3];
   __shared__ uint32_t soff[kRun * 3];                   // each stream's offset from G0
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const size_t wg = wg_base + blockIdx.x;
-  const size_t g = wg / kSplit;
-  const int h0 = (int)(wg % kSplit) * kRun;
-  const size_t t0 = g * kGT + h0;
+  const auto [g, t0, h0, ntl] = run_of(wg_base + blockIdx.x, ntiles);
   if (t0 >= ntiles) return;
-  const int ntl = (int)min((size_t)kRun, ntiles - t0);
   group_offsets(tid, g, ntiles, tsz, gsum, part, toff);
   const uint64_t implied = result[0], head = result[1];
   if (head == 0 || implied != in_len) {                 // the same in every workgroup
@@ -250,22 +288,8 @@ __global__ __launch_bounds__(64 * kPW) void jpr_unpack_tiles(
   if (tid < ntl) {
     const uint32_t off = (uint32_t)(toff[h0 + tid] - G0);       // < 16 x 65,535
     const uint32_t size = (uint32_t)(toff[h0 + tid + 1] - toff[h0 + tid]);
-    bool ok = size <= (uint32_t)kRecMax;
-    uint32_t p = 0, m[3] = {0u, 0u, 0u};
-    for (int c = 0; c < 3 && ok; ++c) {
-      if (p + 4 > size) {
-        ok = false;
-        break;
-      }
-      const uint32_t rle = rd(off + p), nc = rd(off + p + 1);
-      const uint32_t nb = rd(off + p + 2) | rd(off + p + 3) << 8;
-      ok = rle <= slot_codes(c) && nc <= slot_codes(c) && nb <= slot_bits(c);
-      soff[3 * tid + c] = off + p;
-      m[c] = nb | rle << 16 | nc << 24;
-      p += 4u + 3u * nc + ((nb + 7u) >> 3);
-    }
-    ok = ok && p == size;
-    if (!ok) {
+    uint32_t m[3] = {0u, 0u, 0u}, md = 0u;
+    if (!record_rule<false>(rd, off, size, soff + 3 * tid, m, md)) {
       m[0] = m[1] = m[2] = 0u;
       atomicMin(reinterpret_cast<unsigned long long *>(result + 1),
                 1ull + (unsigned long long)(t0 + tid));
@@ -306,6 +330,41 @@ __global__ __launch_bounds__(64 * kPW) void jpr_unpack_tiles(
   }
 }
 
+// jpegr_pack_device and jpegr_pack_tight_device: argument check, sizes, scan, emit
+template <bool kTight>
+int pack(const void *d_bits, const void *d_meta, const void *d_table, int w, int h, int nimg,
+         void *d_out, size_t cap, void *d_out_len, void *d_scratch, void *stream) {
+  const size_t ntiles = tiles_of(w, h, nimg);
+  if (!d_bits || !d_meta || !d_table || !d_out || !d_out_len || !d_scratch || ntiles == 0 ||
+      (reinterpret_cast<uintptr_t>(d_bits) & 3) != 0 || (reinterpret_cast<uintptr_t>(d_meta) & 3) != 0 ||
+      (reinterpret_cast<uintptr_t>(d_table) & 3) != 0 || (reinterpret_cast<uintptr_t>(d_out) & 15) != 0 ||
+      (reinterpret_cast<uintptr_t>(d_out_len) & 7) != 0 ||
+      (reinterpret_cast<uintptr_t>(d_scratch) & 15) != 0)
+    return JPEGR_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const Scratch s = scratch_of(d_scratch, ntiles);
+  auto *bits = static_cast<const uint8_t *>(d_bits);
+  auto *meta = static_cast<const uint32_t *>(d_meta);
+  auto *tab = static_cast<const uint32_t *>(d_table);
+  auto *out = static_cast<uint8_t *>(d_out);
+  if constexpr (kTight)
+    launch_chunks(ntiles, kRun, [&](size_t b, unsigned n) {
+      hipLaunchKernelGGL(jpt_pack_sizes, dim3(n), dim3(64 * kPW), 0, st, meta, tab, ntiles, b, s.tsz, out,
+                         (uint64_t)cap, (uint32_t)w, (uint32_t)h, (uint32_t)nimg);
+    });
+  else
+    launch_chunks(ntiles, 256, [&](size_t b, unsigned n) {
+      hipLaunchKernelGGL(jpr_pack_sizes, dim3(n), dim3(256), 0, st, meta, ntiles, b * 256, s.tsz, out,
+                         (uint64_t)cap, (uint32_t)w, (uint32_t)h, (uint32_t)nimg);
+    });
+  scan(s, ntiles, static_cast<uint64_t *>(d_out_len), st);
+  launch_chunks(ntiles, kRun, [&](size_t b, unsigned n) {
+    hipLaunchKernelGGL(jpr_pack_emit<kTight>, dim3(n), dim3(64 * kPW), 0, st, bits, meta, tab, ntiles, b,
+                       s.tsz, s.gsum, s.part, out, (uint64_t)cap);
+  });
+  return hipGetLastError() == hipSuccess ? JPEGR_OK : JPEGR_ERR_HIP;
+}
+
 }  // namespace
 
 extern "C" size_t jpegr_pack_bound(int w, int h, int nimg) {
@@ -318,49 +377,27 @@ extern "C" size_t jpegr_pack_scratch_bytes(size_t ntiles) {
 }
 
 extern "C" int jpegr_stream_info(const uint8_t header[16], int *w, int *h, int *nimg) {
-  if (!header || !w || !h || !nimg) return JPEGR_ERR_ARG;
-  if (header[0] != 'J' || header[1] != 'P' || header[2] != 'R' || header[3] != '1')
-    return JPEGR_ERR_ARG;
-  uint32_t v[3];
-  for (int i = 0; i < 3; ++i)
-    v[i] = (uint32_t)header[4 + 4 * i] | (uint32_t)header[5 + 4 * i] << 8 |
-           (uint32_t)header[6 + 4 * i] << 16 | (uint32_t)header[7 + 4 * i] << 24;
-  if (v[0] == 0 || v[1] == 0 || v[2] == 0 || v[0] > 0x7FFFFFFFu || v[1] > 0x7FFFFFFFu ||
-      v[2] > 0x7FFFFFFFu)
-    return JPEGR_ERR_ARG;
-  *w = (int)v[0];
-  *h = (int)v[1];
-  *nimg = (int)v[2];
-  return JPEGR_OK;
+  if (!header || !w || !h || !nimg || header[2] != 'R') return JPEGR_ERR_ARG;
+  return parse_header(header, w, h, nimg) ? JPEGR_OK : JPEGR_ERR_ARG;
+}
+
+extern "C" int jpegr_stream_format(const uint8_t header[16], int *w, int *h, int *nimg, int *format) {
+  if (!header || !w || !h || !nimg || !format) return JPEGR_ERR_ARG;
+  const int f = parse_header(header, w, h, nimg);
+  if (f) *format = f;
+  return f ? JPEGR_OK : JPEGR_ERR_ARG;
 }
 
 extern "C" int jpegr_pack_device(const void *d_bits, const void *d_meta, const void *d_table,
                                  int w, int h, int nimg, void *d_out, size_t cap,
                                  void *d_out_len, void *d_scratch, void *stream) {
-  const size_t ntiles = tiles_of(w, h, nimg);
-  if (!d_bits || !d_meta || !d_table || !d_out || !d_out_len || !d_scratch || ntiles == 0 ||
-      (reinterpret_cast<uintptr_t>(d_bits) & 3) != 0 || (reinterpret_cast<uintptr_t>(d_meta) & 3) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_table) & 3) != 0 || (reinterpret_cast<uintptr_t>(d_out) & 15) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_out_len) & 7) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_scratch) & 15) != 0)
-    return JPEGR_ERR_ARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const Scratch s = scratch_of(d_scratch, ntiles);
-  auto *meta = static_cast<const uint32_t *>(d_meta);
-  auto *out = static_cast<uint8_t *>(d_out);
-  for (size_t b = 0; b * 256 < ntiles; b += kMaxWg) {
-    const size_t n = std::min(kMaxWg, (ntiles - b * 256 + 255) / 256);
-    hipLaunchKernelGGL(jpr_pack_sizes, dim3((unsigned)n), dim3(256), 0, st, meta, ntiles, b * 256,
-                       s.tsz, out, (uint64_t)cap, (uint32_t)w, (uint32_t)h, (uint32_t)nimg);
-  }
-  scan(s, ntiles, static_cast<uint64_t *>(d_out_len), st);
-  const size_t nwg = (ntiles + kRun - 1) / kRun;
-  for (size_t b = 0; b < nwg; b += kMaxWg)
-    hipLaunchKernelGGL(jpr_pack_emit, dim3((unsigned)std::min(kMaxWg, nwg - b)), dim3(64 * kPW), 0, st,
-                       static_cast<const uint8_t *>(d_bits), meta,
-                       static_cast<const uint32_t *>(d_table), ntiles, b, s.tsz, s.gsum, s.part, out,
-                       (uint64_t)cap);
-  return hipGetLastError() == hipSuccess ? JPEGR_OK : JPEGR_ERR_HIP;
+  return pack<false>(d_bits, d_meta, d_table, w, h, nimg, d_out, cap, d_out_len, d_scratch, stream);
+}
+
+extern "C" int jpegr_pack_tight_device(const void *d_bits, const void *d_meta, const void *d_table,
+                                       int w, int h, int nimg, void *d_out, size_t cap,
+                                       void *d_out_len, void *d_scratch, void *stream) {
+  return pack<true>(d_bits, d_meta, d_table, w, h, nimg, d_out, cap, d_out_len, d_scratch, stream);
 }
 
 extern "C" int jpegr_unpack_device(const void *d_in, size_t in_len, int w, int h, int nimg,
@@ -377,17 +414,15 @@ extern "C" int jpegr_unpack_device(const void *d_in, size_t in_len, int w, int h
   const Scratch s = scratch_of(d_scratch, ntiles);
   auto *in = static_cast<const uint8_t *>(d_in);
   auto *result = static_cast<uint64_t *>(d_result);
-  for (size_t b = 0; b * 256 < ntiles; b += kMaxWg) {
-    const size_t n = std::min(kMaxWg, (ntiles - b * 256 + 255) / 256);
-    hipLaunchKernelGGL(jpr_unpack_sizes, dim3((unsigned)n), dim3(256), 0, st, in, (uint64_t)in_len,
-                       ntiles, b * 256, (uint32_t)w, (uint32_t)h, (uint32_t)nimg, s.tsz, result);
-  }
+  launch_chunks(ntiles, 256, [&](size_t b, unsigned n) {
+    hipLaunchKernelGGL(jpr_unpack_sizes, dim3(n), dim3(256), 0, st, in, (uint64_t)in_len, ntiles, b * 256,
+                       (uint32_t)w, (uint32_t)h, (uint32_t)nimg, s.tsz, result);
+  });
   scan(s, ntiles, result, st);
-  const size_t nwg = (ntiles + kRun - 1) / kRun;
-  for (size_t b = 0; b < nwg; b += kMaxWg)
-    hipLaunchKernelGGL(jpr_unpack_tiles, dim3((unsigned)std::min(kMaxWg, nwg - b)), dim3(64 * kPW), 0, st,
-                       in, (uint64_t)in_len, ntiles, b, s.tsz, s.gsum, s.part, result,
-                       static_cast<uint8_t *>(d_bits), static_cast<uint32_t *>(d_meta),
-                       static_cast<uint32_t *>(d_table));
+  launch_chunks(ntiles, kRun, [&](size_t b, unsigned n) {
+    hipLaunchKernelGGL(jpr_unpack_tiles, dim3(n), dim3(64 * kPW), 0, st, in, (uint64_t)in_len, ntiles, b,
+                       s.tsz, s.gsum, s.part, result, static_cast<uint8_t *>(d_bits),
+                       static_cast<uint32_t *>(d_meta), static_cast<uint32_t *>(d_table));
+  });
   return hipGetLastError() == hipSuccess ? JPEGR_OK : JPEGR_ERR_HIP;
 }

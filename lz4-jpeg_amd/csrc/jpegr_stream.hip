@@ -2,8 +2,9 @@
 // JPT1 (include/jpegr.h): tiles [tile0, tile0 + ntile) of a stream to
 // coefficients, no slots in between.  The format is the header's, one for the
 // launch: jprs_decode branches once into the record routine of that format
-// (decode_record<kTight>; the JPR1 instantiation is the code it was before JPT1
-// existed).
+// (decode_record<kTight>).  The index and header reader and the
+// rule that makes a record malformed are the ones unpack uses
+// (jpegr_pack_common.h: get_index, header_ok, record_rule).
 //
 //   jprs_sizes    index -> u32 sizes (the scan's input), the header verdict in
 //                 result[1], result[2] = 0: the call's first launch initialises
@@ -48,15 +49,9 @@ __global__ __launch_bounds__(256) void jprs_sizes(const uint8_t *__restrict__ in
                                                   uint64_t *__restrict__ result) {
   const size_t t = t_base + (size_t)blockIdx.x * 256 + threadIdx.x;
   if (t >= ntiles) return;
-  const uint64_t pos = kHdr + 2 * (uint64_t)t;
-  const uint32_t lo = pos < in_len ? in[pos] : 0u, hi = pos + 1 < in_len ? in[pos + 1] : 0u;
-  tsz[t] = lo | hi << 8;
+  tsz[t] = get_index(in, in_len, t);
   if (t == 0) {
-    const uint32_t want[4] = {0x3152504Au /* "JPR1" */, w, h, nimg};
-    bool ok = in_len >= kHdr + 2 * (uint64_t)ntiles;
-    for (uint32_t i = 0; ok && i < (uint32_t)kHdr; ++i)
-      ok = in[i] == (uint8_t)(want[i >> 2] >> (8 * (i & 3))) || (i == 2 && in[i] == 'T');   // or "JPT1"
-    result[1] = ok ? ~0ull : 0ull;
+    result[1] = header_ok(in, in_len, ntiles, w, h, nimg, true) ? ~0ull : 0ull;
     result[2] = 0ull;
   }
 }
@@ -447,40 +442,16 @@ __device__ __forceinline__ uint32_t sdecode_wave(SDecLds<kLuma ? 64 : 32, kLuma 
   return fails;
 }
 
-// A lane's record of `size` bytes at rec, tile t of the stream: the three
-// stream headers against the slots' bounds and the indexed size
-// (jpr_unpack_tiles' record rules; in a JPT1 record the table's bytes follow
-// from the mode in the top two bits of the u16, and mode 3 is malformed); each
-// header is read only once it is known to lie inside the record.  Then the
-// wave's channel group is decoded.
+// A lane's record of `size` bytes at rec, tile t of the stream: checked by
+// the rule every reader shares (record_rule, jpegr_pack_common.h), whose reads
+// stay inside the record; then the wave's channel group is decoded.
 template <bool kTight>
 __device__ __forceinline__ void decode_record(SDecLds<64, kFastCap> &SY, SDecLds<32, kChromaCap> &SC,
                                               int lane, int wv, const uint8_t *rec, uint32_t size,
                                               size_t t, uint64_t *__restrict__ result,
                                               int16_t *__restrict__ tile_out) {
-  bool good = size <= (uint32_t)kRecMax;
-  uint32_t p = 0, so[3] = {0u, 0u, 0u}, m[3] = {0u, 0u, 0u}, md = 0u;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    good = good && p + 4 <= size;
-    if (good) {
-      const uint32_t rle = rec[p], nc = rec[p + 1];
-      uint32_t nb = (uint32_t)rec[p + 2] | (uint32_t)rec[p + 3] << 8;
-      uint32_t tbytes = 3u * nc;
-      if constexpr (kTight) {
-        const uint32_t mode = nb >> 14;
-        nb &= 0x3FFFu;
-        good = mode != 3u;
-        if (mode) tbytes = ((nc + 1u) >> 1) + mode * nc;
-        md |= mode << (2 * c);
-      }
-      good = good && rle <= slot_codes(c) && nc <= slot_codes(c) && nb <= slot_bits(c);
-      so[c] = p;
-      m[c] = nb | rle << 16 | nc << 24;
-      p += 4u + tbytes + ((nb + 7u) >> 3);
-    }
-  }
-  good = good && p == size;
+  uint32_t so[3] = {0u, 0u, 0u}, m[3] = {0u, 0u, 0u}, md = 0u;
+  const bool good = record_rule<kTight>([&](uint32_t x) -> uint32_t { return rec[x]; }, 0u, size, so, m, md);
   uint32_t fails;
   if (__builtin_amdgcn_readfirstlane(wv) == 0) {
     if (!good)
@@ -553,16 +524,14 @@ extern "C" int jpegr_stream_decode_device(const void *d_in, size_t in_len, int w
   const Scratch s = scratch_of(d_scratch, ntiles);
   auto *in = static_cast<const uint8_t *>(d_in);
   auto *result = static_cast<uint64_t *>(d_result);
-  for (size_t b = 0; b * 256 < ntiles; b += kMaxWg) {
-    const size_t n = std::min(kMaxWg, (ntiles - b * 256 + 255) / 256);
-    hipLaunchKernelGGL(jprs_sizes, dim3((unsigned)n), dim3(256), 0, st, in, (uint64_t)in_len, ntiles,
-                       b * 256, (uint32_t)w, (uint32_t)h, (uint32_t)nimg, s.tsz, result);
-  }
+  launch_chunks(ntiles, 256, [&](size_t b, unsigned n) {
+    hipLaunchKernelGGL(jprs_sizes, dim3(n), dim3(256), 0, st, in, (uint64_t)in_len, ntiles, b * 256,
+                       (uint32_t)w, (uint32_t)h, (uint32_t)nimg, s.tsz, result);
+  });
   scan(s, ntiles, result, st);
-  const size_t nwg = (ntile + kLanes - 1) / kLanes;
-  for (size_t b = 0; b < nwg; b += kMaxWg)
-    hipLaunchKernelGGL(jprs_decode, dim3((unsigned)std::min(kMaxWg, nwg - b)), dim3(2 * kLanes), 0, st,
-                       in, (uint64_t)in_len, ntiles, tile0, ntile, b, s.tsz, s.gsum, s.part, result,
-                       static_cast<int16_t *>(d_coef));
+  launch_chunks(ntile, kLanes, [&](size_t b, unsigned n) {
+    hipLaunchKernelGGL(jprs_decode, dim3(n), dim3(2 * kLanes), 0, st, in, (uint64_t)in_len, ntiles, tile0,
+                       ntile, b, s.tsz, s.gsum, s.part, result, static_cast<int16_t *>(d_coef));
+  });
   return hipGetLastError() == hipSuccess ? JPEGR_OK : JPEGR_ERR_HIP;
 }

@@ -18,8 +18,9 @@
 //   jps_sizes          a lane per tile: record size -> u32 (scan input), the
 //                      u16 index, the 16-B header
 //   lz4_scan_reduce / lz4_scan_partials (lz4r_scan.h, as they are)
-//   jps_place          jpr_pack_emit's LDS image of 16 tiles' output range,
-//                      each stream read from its arena position
+//   jps_place          jpr_pack_emit's run of 16 tiles, LDS image of their
+//                      output range and flush (jpegr_pack_common.h: run_of,
+//                      image_out), each stream read from its arena position
 //   jps_repair         exits at once unless the first pass dropped a stream
 //                      (cap is short of the stream): then a dropped stream
 //                      of a tile that starts below cap is encoded again, by
@@ -90,11 +91,6 @@ __global__ void jps_init(uint64_t *__restrict__ ctrl, uint64_t *__restrict__ res
   if (threadIdx.x < 2) result[threadIdx.x] = 0;
 }
 
-// table bytes of n entries in JPT1 mode md (mode 0: JPR1's entries)
-__device__ __forceinline__ uint32_t table_bytes(uint32_t n, uint32_t md) {
-  return md == 0 ? 3u * n : ((n + 1u) >> 1) + md * n;
-}
-
 // One working set of the hashed encoder (jpegr_entropy.hip's layout) and,
 // behind it, what the slot encoder writes to global slots: the stream's bits,
 // table and meta word.
@@ -123,17 +119,16 @@ __device__ __forceinline__ Hashed hashed_encode(const int16_t *__restrict__ coef
                                                lb + kBitsO, bits_cap(cc), ref_bits_max(cc), stab,
                                                reinterpret_cast<uint32_t *>(lb + kMetaO));
   e.m = *reinterpret_cast<const uint32_t *>(lb + kMetaO);
-  e.nc = min(e.m >> 24, slot_codes(cc));
-  e.nb = min(e.m & 0xFFFFu, slot_bits(cc));
+  e.nc = meta_codes(e.m, cc);
+  e.nb = meta_bits(e.m, cc);
   e.mode = 0;
-  if (tight && e.nc) {
+  if (tight) {
     bool lng = false, wide = false;
     for (uint32_t i = 0; i < e.nc; ++i) {
-      const uint32_t x = stab[i];
-      lng = lng || ((x >> 16) & 255u) > 15u;
-      wide = wide || (int16_t)x != (int8_t)x;
+      lng = lng || long_len(stab[i]);
+      wide = wide || wide_val(stab[i]);
     }
-    e.mode = lng ? 0u : wide ? 2u : 1u;
+    e.mode = table_mode(e.nc, lng, wide);
   }
   e.tb = table_bytes(e.nc, e.mode);
   e.size = 4u + e.tb + ((e.nb + 7u) >> 3);
@@ -143,7 +138,7 @@ __device__ __forceinline__ Hashed hashed_encode(const int16_t *__restrict__ coef
 // the stream's e.size bytes to d (global or LDS), one by one
 __device__ __forceinline__ void put_stream(uint8_t *d, const Hashed &e, const uint8_t *lb) {
   const uint32_t *const stab = reinterpret_cast<const uint32_t *>(lb + kTabO);
-  const uint32_t hw = ((e.m >> 16) & 255u) | e.nc << 8 | (e.nb | e.mode << 14) << 16;
+  const uint32_t hw = stream_header((e.m >> 16) & 255u, e.nc, e.nb, e.mode);
   for (uint32_t i = 0; i < 4; ++i) d[i] = (uint8_t)(hw >> (8 * i));
   uint8_t *p = d + 4;
   if (e.mode == 0u) {
@@ -387,8 +382,7 @@ __global__ __launch_bounds__(kLanes) void stream_encode_lane(const EncArgs a) {
     // lane is byte 3 - (b & 3) of row b / 4 counted from row BitRow - q.
     uint8_t *const hb = brow - q * (4 * kLanes);
     auto sbyte = [&](uint32_t b) -> uint8_t & { return hb[(b >> 2) * (4 * kLanes) + (3u - (b & 3u))]; };
-    *reinterpret_cast<uint32_t *>(hb) = __builtin_bswap32(
-        (uint32_t)R | (uint32_t)U << 8 | (nb | mode << 14) << 16);
+    *reinterpret_cast<uint32_t *>(hb) = __builtin_bswap32(stream_header((uint32_t)R, (uint32_t)U, nb, mode));
     if (mode == 0u) {
 #pragma unroll
       for (int k = 0; k < Cap; ++k)
@@ -481,7 +475,7 @@ __global__ __launch_bounds__(kLanes) void stream_encode_lane(const EncArgs a) {
   }
 }
 
-// jpr_pack_sizes with the sizes from the directory
+// jpr_pack_sizes' job with the sizes from the directory
 __global__ __launch_bounds__(256) void jps_sizes(const uint64_t *__restrict__ dir, size_t ntiles,
                                                  size_t t_base, uint32_t *__restrict__ tsz,
                                                  uint8_t *__restrict__ out, uint64_t cap,
@@ -492,32 +486,18 @@ __global__ __launch_bounds__(256) void jps_sizes(const uint64_t *__restrict__ di
   const uint32_t sz = (uint32_t)(dir[3 * t] & 0xFFFFu) + (uint32_t)(dir[3 * t + 1] & 0xFFFFu) +
                       (uint32_t)(dir[3 * t + 2] & 0xFFFFu);
   tsz[t] = sz;
-  const uint64_t pos = kHdr + 2 * (uint64_t)t;          // 2-B aligned: out is 16-B aligned
-  if (pos + 2 <= cap)
-    *reinterpret_cast<uint16_t *>(out + pos) = (uint16_t)sz;
-  else if (pos < cap)
-    out[pos] = (uint8_t)sz;
-  if (t == 0) {
-    const uint32_t hw[4] = {magic, w, h, nimg};
-    for (uint32_t i = 0; i < (uint32_t)kHdr && i < cap; ++i) out[i] = (uint8_t)(hw[i >> 2] >> (8 * (i & 3)));
-  }
+  put_index(out, cap, t, sz);
+  if (t == 0) put_header(out, cap, magic, w, h, nimg);
 }
 
-// jpr_pack_emit's run: 16 tiles per workgroup, 4 waves of 4 tiles
-constexpr int kRun = 16;
-constexpr int kSplit = kGT / kRun;
-constexpr int kPW = 4;
-constexpr int kTW = kRun / kPW;
-constexpr int kImg = kRun * kRecMax + 16;
-static_assert(kGT % kRun == 0 && kRun % kPW == 0 && kImg % 16 == 0, "whole workgroups per scan group");
-
-// jpr_pack_emit (its comments hold here) with each stream read from the
-// arena: a stream is whole dwords at a dword address, so lane l takes dword
-// l (and l + 64, ...) of each of the tile's three streams, the first round of
-// all four tiles in flight before any is stored.  Only tiles that start below
-// cap are read: the others' bytes are clipped anyway.  The bytes of a stream
-// that the arena dropped are left as the image holds them; jps_repair writes
-// them afterwards.  Workgroup 0 copies the length to the result.
+// jpr_pack_emit's run, LDS image and flush (jpegr_pack_common.h) with each
+// stream read from the arena: a stream is whole dwords at a dword address, so
+// lane l takes dword l (and l + 64, ...) of each of the tile's three streams,
+// the first round of all four tiles in flight before any is stored.  Only
+// tiles that start below cap are read: the others' bytes are clipped anyway.
+// The bytes of a stream that the arena dropped are left as the image holds
+// them; jps_repair writes them afterwards.  Workgroup 0 copies the length to
+// the result.
 __global__ __launch_bounds__(64 * kPW) void jps_place(
     const uint64_t *__restrict__ dir, const uint32_t *__restrict__ arena, uint64_t arena_dwords,
     size_t ntiles, size_t wg_base, const uint32_t *__restrict__ tsz,
@@ -529,11 +509,8 @@ __global__ __launch_bounds__(64 * kPW) void jps_place(
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const size_t wg = wg_base + blockIdx.x;
   if (wg == 0 && tid == 0) result[0] = *out_len;
-  const size_t g = wg / kSplit;
-  const int h0 = (int)(wg % kSplit) * kRun;
-  const size_t t0 = g * kGT + h0;                       // the workgroup's first tile
+  const auto [g, t0, h0, ntl] = run_of(wg, ntiles);
   if (t0 >= ntiles) return;
-  const int ntl = (int)min((size_t)kRun, ntiles - t0);
   group_offsets(tid, g, ntiles, tsz, gsum, part, toff);
   __syncthreads();
   const uint64_t G0 = toff[h0], G1 = toff[h0 + ntl];
@@ -578,21 +555,7 @@ __global__ __launch_bounds__(64 * kPW) void jps_place(
     }
   }
   __syncthreads();
-  // ---- LDS image -> stream: aligned 16-B stores; the first and last partial
-  // chunks, which neighbouring workgroups share, a byte per lane; nothing at
-  // or past cap
-  const uint64_t E = min(G1, cap);
-  uint8_t *const outF = out + (G0 - lead);              // 16-B aligned
-  const uint32_t nrel = (uint32_t)(E - G0) + lead;
-  const uint32_t c0 = lead ? 1u : 0u, c1 = nrel >> 4;   // the whole chunks: [c0, c1)
-  for (uint32_t ci = c0 + (uint32_t)tid; ci < c1; ci += 64 * kPW)
-    __builtin_nontemporal_store(reinterpret_cast<const u32x4 *>(img)[ci],
-                                reinterpret_cast<u32x4 *>(outF + 16u * ci));
-  if (wv == kPW - 1 && lane < 32) {
-    const uint32_t x = lane < 16 ? (uint32_t)lane : 16u * c1 + (uint32_t)(lane - 16);
-    const bool own = lane < 16 ? (c0 && x >= lead && x < nrel) : (c1 >= c0 && x < nrel);
-    if (own) outF[x] = img[x];
-  }
+  image_out(img, tid, lane, wv, G0, G1, lead, out, cap);
 }
 
 // A wave per scan group, after place, and only when the first pass dropped
@@ -641,16 +604,14 @@ template <bool kTight>
 void launch_encode(const EncArgs &a0, hipStream_t st) {
   EncArgs a = a0;
   const size_t groups = (a.ntiles + kLanes - 1) / kLanes;
-  for (size_t b = 0; b < groups; b += kMaxWg) {
+  launch_chunks(groups, 1, [&](size_t b, unsigned n) {
     a.wg_base = b;
-    hipLaunchKernelGGL((stream_encode_lane<true, kTight>),
-                       dim3((unsigned)std::min(kMaxWg, groups - b)), dim3(kLanes), 0, st, a);
-  }
-  for (size_t b = 0; b < 2 * groups; b += kMaxWg) {
+    hipLaunchKernelGGL((stream_encode_lane<true, kTight>), dim3(n), dim3(kLanes), 0, st, a);
+  });
+  launch_chunks(2 * groups, 1, [&](size_t b, unsigned n) {
     a.wg_base = b;
-    hipLaunchKernelGGL((stream_encode_lane<false, kTight>),
-                       dim3((unsigned)std::min(kMaxWg, 2 * groups - b)), dim3(kLanes), 0, st, a);
-  }
+    hipLaunchKernelGGL((stream_encode_lane<false, kTight>), dim3(n), dim3(kLanes), 0, st, a);
+  });
 }
 
 }  // namespace
@@ -691,22 +652,20 @@ extern "C" int jpegr_stream_encode_device(const void *d_coef, int w, int h, int 
   hipLaunchKernelGGL(jps_init, dim3(1), dim3(64), 0, st, s.ctrl, result);
   if (tight) launch_encode<true>(a, st);
   else launch_encode<false>(a, st);
-  for (size_t b = 0; b * 256 < ntiles; b += kMaxWg) {
-    const size_t n = std::min(kMaxWg, (ntiles - b * 256 + 255) / 256);
-    hipLaunchKernelGGL(jps_sizes, dim3((unsigned)n), dim3(256), 0, st, s.dir, ntiles, b * 256,
-                       s.scan.tsz, out, (uint64_t)cap, tight ? 0x3154504Au : 0x3152504Au,
-                       (uint32_t)w, (uint32_t)h, (uint32_t)nimg);
-  }
+  launch_chunks(ntiles, 256, [&](size_t b, unsigned n) {
+    hipLaunchKernelGGL(jps_sizes, dim3(n), dim3(256), 0, st, s.dir, ntiles, b * 256, s.scan.tsz, out,
+                       (uint64_t)cap, tight ? kMagicJPT1 : kMagicJPR1, (uint32_t)w, (uint32_t)h,
+                       (uint32_t)nimg);
+  });
   scan(s.scan, ntiles, static_cast<uint64_t *>(d_out_len), st);
-  const size_t nwg = (ntiles + kRun - 1) / kRun;
-  for (size_t b = 0; b < nwg; b += kMaxWg)
-    hipLaunchKernelGGL(jps_place, dim3((unsigned)std::min(kMaxWg, nwg - b)), dim3(64 * kPW), 0, st,
-                       s.dir, s.arena, s.arena_dwords, ntiles, b, s.scan.tsz, s.scan.gsum, s.scan.part,
-                       out, (uint64_t)cap, static_cast<const uint64_t *>(d_out_len), result);
-  const size_t ngroups = (ntiles + kGT - 1) / kGT;
-  for (size_t b = 0; b < ngroups; b += kMaxWg)
-    hipLaunchKernelGGL(jps_repair, dim3((unsigned)std::min(kMaxWg, ngroups - b)), dim3(kLanes), 0, st,
-                       s.dir, a.coef, ntiles, b, s.scan.tsz, s.scan.gsum, s.scan.part, s.ctrl, tight, out,
-                       (uint64_t)cap);
+  launch_chunks(ntiles, kRun, [&](size_t b, unsigned n) {
+    hipLaunchKernelGGL(jps_place, dim3(n), dim3(64 * kPW), 0, st, s.dir, s.arena, s.arena_dwords, ntiles, b,
+                       s.scan.tsz, s.scan.gsum, s.scan.part, out, (uint64_t)cap,
+                       static_cast<const uint64_t *>(d_out_len), result);
+  });
+  launch_chunks(ntiles, kGT, [&](size_t b, unsigned n) {
+    hipLaunchKernelGGL(jps_repair, dim3(n), dim3(kLanes), 0, st, s.dir, a.coef, ntiles, b, s.scan.tsz,
+                       s.scan.gsum, s.scan.part, s.ctrl, tight, out, (uint64_t)cap);
+  });
   return hipGetLastError() == hipSuccess ? JPEGR_OK : JPEGR_ERR_HIP;
 }

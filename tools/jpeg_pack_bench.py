@@ -30,8 +30,8 @@ the direct decode; and the device bytes a 4K decode needs either way.  With
 packs and the direct decode of each stream, alternated over --rounds rounds in
 this run after the same pre-warm and settle; both streams' lengths and bytes
 per tile; every output checked (the tight stream decodes to the coefficients
-the entropy stage was given).  --against LIB adds the JPR1 calls -- pack,
-unpack, direct decode -- of a second build of the library (the parent
+the entropy stage was given).  --against LIB adds the same calls -- both packs,
+unpack, both direct decodes -- of a second build of the library (the parent
 commit's, loaded beside the product's with RTLD_LOCAL) to the same rounds, and
 prints each pair with the ratio of the medians.  With --once N: N launches of
 the two packs and the two direct decodes per image and nothing else.
@@ -41,10 +41,10 @@ formats, for profiles/jpr_stream_encode.log: beside entropy encode + pack and
 entropy encode + tight pack, the stages it replaces, alternated over --rounds
 rounds in this run after the same pre-warm and settle; every output checked
 against the two-stage stream.  --against LIB adds the second build's entropy
-encode / decode, both packs and the direct decode to the same rounds, with the
-ratio of the medians per pair.  Then the device memory compress_device peaks
-at, direct or not, for one image and for eight.  With --once N: N direct
-encodes of each format per image and nothing else."""
+encode / decode, both packs, both direct encodes and the direct decode to the
+same rounds, with the ratio of the medians per pair.  Then the device memory
+compress_device peaks at, direct or not, for one image and for eight.  With
+--once N: N direct encodes of each format per image and nothing else."""
 import argparse
 import json
 import os
@@ -281,15 +281,20 @@ def tight_side(args, torch, jpeg, name, ent, d_coef, other):
     if other is not None:
         par = Calls(other, torch, ent, nt, d_coef)
         par.pack()
-        par.n = int(par.len.item())
+        par.pack_tight()
+        par.n, par.n_t = int(par.len.item()), int(par.len_t.item())
         par.unpack()
         par.direct()
+        par.direct_tight()
         torch.cuda.synchronize()
         res["against_outputs_equal"] = par.n == prod.n and bool(torch.equal(par.out[:par.n], prod.out[:prod.n])) \
+            and par.n_t == prod.n_t and bool(torch.equal(par.out_t[:par.n_t], prod.out_t[:prod.n_t])) \
             and bool(torch.equal(par.coef, prod.coef)) and par.res3.cpu().tolist() == prod.res3.cpu().tolist() \
+            and bool(torch.equal(par.coef_t, prod.coef_t)) and par.res3_t.cpu().tolist() == prod.res3_t.cpu().tolist() \
             and all(bool(torch.equal(getattr(par.back, f), getattr(prod.back, f))) for f in ("bits", "meta", "table"))
-        calls += [("against_pack", par.pack), ("against_unpack", par.unpack),
-                  ("against_stream_decode", par.direct)]
+        calls += [("against_pack", par.pack), ("against_pack_tight", par.pack_tight),
+                  ("against_unpack", par.unpack), ("against_stream_decode", par.direct),
+                  ("against_stream_decode_tight", par.direct_tight)]
     ms = {k: [] for k, _ in calls}
     for r in range(args.rounds):                      # alternated; the order turns with the round
         for key, fn in calls[r % len(calls):] + calls[:r % len(calls)]:
@@ -298,7 +303,7 @@ def tight_side(args, torch, jpeg, name, ent, d_coef, other):
     for key, _ in calls:
         res[key + "_ms"] = spread(ms[key])
     if other is not None:
-        for key in ("pack", "unpack", "stream_decode"):
+        for key in ("pack", "pack_tight", "unpack", "stream_decode", "stream_decode_tight"):
             res[key + "_over_against"] = round(
                 res[key + "_ms"]["median"] / res["against_" + key + "_ms"]["median"], 4)
     print(json.dumps(res), flush=True)
@@ -438,11 +443,15 @@ def direct_side(args, torch, jpeg, name, img, d_coef, other):
              ("two_stage", prod.two_stage), ("two_stage_tight", prod.two_stage_tight),
              ("stream_encode", prod.direct), ("stream_encode_tight", prod.direct_tight),
              ("entropy_decode", prod.entropy_decode), ("stream_decode", prod.stream_decode)]
-    shared = ("entropy_encode", "pack", "pack_tight", "entropy_decode", "stream_decode")
+    shared = ("entropy_encode", "pack", "pack_tight", "entropy_decode", "stream_decode",
+              "stream_encode", "stream_encode_tight")
     if other is not None:
         par = EncCalls(other, torch, nt, d_coef, jpeg)
+        par.stream_encode, par.stream_encode_tight = par.direct, par.direct_tight
         par.two_stage()
         par.pack_tight()
+        par.direct()
+        par.direct_tight()
         torch.cuda.synchronize()
         par.n = int(par.len["r"].item())
         par.stream_decode()
@@ -451,6 +460,8 @@ def direct_side(args, torch, jpeg, name, img, d_coef, other):
         res["against_outputs_equal"] = par.n == n["r"] and int(par.len["t"].item()) == n["t"] \
             and bool(torch.equal(par.out["r"][:par.n], prod.out["r"][:par.n])) \
             and bool(torch.equal(par.out["t"][:n["t"]], prod.out["t"][:n["t"]])) \
+            and bool(torch.equal(par.out["dr"][:par.n], prod.out["r"][:par.n])) \
+            and bool(torch.equal(par.out["dt"][:n["t"]], prod.out["t"][:n["t"]])) \
             and bool(torch.equal(par.coef, d_coef)) and bool(torch.equal(par.coef2, d_coef))
         calls += [("against_" + k, getattr(par, k)) for k in shared]
     ms = {k: [] for k, _ in calls}

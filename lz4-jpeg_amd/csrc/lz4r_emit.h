@@ -4,14 +4,24 @@
 //   offsets  the blocks' stream offsets from the partials, the group sums and
 //            a wave scan; also stored to boff (the decoder's side input)
 //   stage    the 32 blocks' input -> LDS (the literals' source; 16-B loads)
-//   bytes    each wave takes 8 blocks and flattens their sequence records over
-//            the lanes (one round = 64 sequences of one or more blocks); per
-//            sequence the token / size / literal-extension / offset /
-//            match-extension bytes (write_sequence, LZ4.c:365-413) and per
-//            block the u8 count + u16 size header (write_block, :415-425)
-//            land by aligned ds_or in a zeroed LDS image of the output range,
-//            and the literal runs are flattened over the lanes as aligned
-//            16-byte image words funnel-shifted out of the staged input
+//   bytes    the 32 blocks' sequence records, block after block, take the
+//            flattened indices 0 .. T-1 (T = 496 on text) and are dealt in
+//            rounds of 64 to the 8 waves, round r to wave r % 8: no wave runs
+//            a second, nearly empty round for its own blocks' stragglers.
+//            Every wave scans the 32 counts for itself; a round finds each
+//            lane's block by a max-scan over the block starts inside it, the
+//            literal-run start of its first record in the record before it
+//            (LDS head or overflow slot), and its first token's place with no
+//            word from another wave: at a block's offset + 3 when one starts
+//            there, else at the next block's offset less the round's bytes to
+//            that block's end (a block that holds a whole round sums its own
+//            earlier records: > 64 records, none in text).  Per sequence the
+//            token / size / literal-extension / offset / match-extension bytes
+//            (write_sequence, LZ4.c:365-413) and per block the u8 count + u16
+//            size header (write_block, :415-425) land by aligned ds_or in a
+//            zeroed LDS image of the output range, and each round's literal
+//            runs are flattened over the lanes as aligned 16-byte image words
+//            funnel-shifted out of the staged input
 //   store    the image -> the stream as aligned 16-B stores (the edge chunks
 //            bytewise); nothing at or past `cap` is written.
 // This is the emission lz4_tiles used to do one block per wave; here a round
@@ -34,7 +44,7 @@
 namespace {
 
 constexpr int kGH = 32;                              // blocks per emit workgroup
-constexpr int kEW = 8;                               // waves per emit workgroup (4 blocks each)
+constexpr int kEW = 8;                               // waves per emit workgroup
 constexpr int kRecPre = kHeadW;                      // record dwords per block staged in LDS
 constexpr int kGSplit = kGT / kGH;                   // workgroups per group
 constexpr int kEmitImg = kGH * kBlkOutMax + 32;      // worst case: every block 548 B
@@ -50,9 +60,30 @@ __device__ __forceinline__ void or_bytes(uint32_t *buf32, int x, uint32_t v) {
   atomicOr(&buf32[(x >> 2) + 1], (uint32_t)(w >> 32));
 }
 
-// Records -> bytes of one emit task (lz4_emit): wave wv takes
-// blocks [h0 + 4 wv, ...) of the task's [h0, h1); the image img[lead] is
-// stream byte G0; block h's input is stage[kStagePad + 300 (h - h0) + p].
+// One record (lz4r_layout.h) of workgroup block b (0 .. kGH-1), k its index in
+// the block: the head staged in LDS, or the block's overflow slot
+__device__ __forceinline__ uint32_t load_record(const uint32_t (*recst)[kRecPre],
+                                                const uint8_t *__restrict__ wovf, int b, int k) {
+  const uint32_t *rp = reinterpret_cast<const uint32_t *>(wovf + b * kOvf);
+  return 1 + k < kRecPre ? recst[b][1 + k] : rp[1 + k - kRecPre];
+}
+
+// The stream bytes of the sequence with record r whose literal run starts at
+// block byte pend: token, u16 size, literal extension, literals, u16 offset,
+// match extension (write_sequence, LZ4.c:365-413)
+__device__ __forceinline__ int sequence_bytes(uint32_t r, int pend) {
+  const int M = (int)((r >> 9) & 255u);
+  const int L = (int)(r >> 19) - M - pend;
+  const int le = L >= 15 ? ((((L - 15) & 255) == 255) ? 2 : 1) : 0;
+  const int mx = (M - 4) & 255;
+  return 5 + le + L + (M >= 4 && mx >= 15 ? 1 : 0);
+}
+
+// Records -> bytes of one emit task (lz4_emit), blocks [h0, h1) of a group:
+// the task's records, block after block, take the flattened indices 0 .. T-1
+// and wave wv takes the rounds wv, wv + 8, ... of 64 records each; the image
+// img[lead] is stream byte G0; block h's input is
+// stage[kStagePad + 300 (h - h0) + p].
 __device__ __forceinline__ void emit_records(const int wv, const int lane, const int h0,
                                              const int h1, const uint64_t G0, const int lead,
                                              const uint64_t *toff, uint8_t *img,
@@ -60,119 +91,147 @@ __device__ __forceinline__ void emit_records(const int wv, const int lane, const
                                              const uint32_t (*recst)[kRecPre],
                                              uint32_t (*marks)[64], const uint4 *pmask,
                                              const uint8_t *__restrict__ wovf) {
-  {
-    constexpr int kBW = kGH / kEW;                   // blocks per wave
-    const int bl0 = h0 + wv * kBW, bl1 = min(h1, bl0 + kBW);
-    if (bl0 < bl1) {
-      uint32_t *const out32 = reinterpret_cast<uint32_t *>(img);
-      const int nbk = bl1 - bl0;
-      // lanes 0..nbk-1: the blocks' sequence counts -> first flattened index
-      const uint32_t hd = lane < nbk ? recst[bl0 - h0 + lane][0] : 0u;
-      const uint32_t ns = hd >> 16;
-      const uint32_t sinc = wave_incl_add(ns);
-      const int Stot = (int)lane63(sinc);
-      const int sst = (int)(sinc - ns);
-      int st[kBW];                                 // wave-uniform block starts
-#pragma unroll
-      for (int i = 0; i < kBW; ++i)
-        st[i] = i < nbk ? __builtin_amdgcn_readlane(sst, i) : 0x7fffffff;
-      // the wave's blocks are contiguous in the image, each its 3 header bytes
-      // and then its sequences' bytes (tsz counts the bytes written): sequence f
-      // lands at the wave's first image byte + 3 (its block's rank + 1) + the
-      // bytes of the wave's sequences before it
-      int end_prev = 0, wcur = lead + (int)(toff[bl0] - G0) + 3;
-      for (int f0 = 0; f0 < Stot; f0 += 64) {
-        const int f = f0 + lane;
-        const bool valid = f < Stot;
-        int bi = 0, sb = 0;                        // the lane's block: the last start <= f
-#pragma unroll
-        for (int i = 1; i < kBW; ++i) {
-          const bool ge = f >= st[i];
-          bi += ge ? 1 : 0;
-          sb = ge ? st[i] : sb;
+  uint32_t *const out32 = reinterpret_cast<uint32_t *>(img);
+  // lanes 0..h1-h0-1: the blocks' sequence counts (>= 1) -> first flattened
+  // index; every wave scans for itself (32 counts: cheaper than a barrier)
+  const uint32_t ns = lane < h1 - h0 ? recst[lane][0] >> 16 : 0u;
+  const uint32_t sinc = wave_incl_add(ns);
+  const int T = (int)lane63(sinc);
+  const uint32_t sst = sinc - ns;              // (the lanes past the blocks: T)
+  // a block's start as one word that grows with the block: a wave max-scan
+  // over the starts of a round hands every lane its block and that block's
+  // first index
+  const uint32_t desc = ns ? ((uint32_t)(lane + 1) << 16) | sst : 0u;
+  // the task's blocks are contiguous in the image, each its 3 header bytes
+  // and then its sequences' bytes (tsz counts the bytes written): sequence f
+  // of a round lands at the round's first one + 3 per block start between
+  // them + the bytes of the round's sequences before it
+  const int rel = lead - (int)(uint32_t)G0;    // image byte = rel + (u32) stream byte
+  const int wvu = __builtin_amdgcn_readfirstlane(wv);   // (a VGPR otherwise: f0 uniform)
+  const uint32_t *const toff32 = reinterpret_cast<const uint32_t *>(toff);
+  for (int f0 = 64 * wvu; f0 < T; f0 += 64 * kEW) {
+    const bool valid = f0 + lane < T;
+    // block cb holds record f0 (k0 of it): the last start <= f0
+    const int cb = __builtin_popcountll(ballot(sst <= (uint32_t)f0)) - 1;
+    const uint32_t cd = (uint32_t)__builtin_amdgcn_readlane((int)desc, cb);
+    const int k0 = f0 - (int)(cd & 0xFFFFu);
+    const int cn = __builtin_amdgcn_readlane((int)sinc, cb) - f0;   // its records from f0 on
+    // the round's uniform reads, under the marks' round trip: the offset
+    // of the first block boundary at or after f0, and the record before
+    // f0 (where the first literal run starts: the head, or the overflow
+    // slot from record 24 on)
+    const int nz = k0 != 0 ? 1 : 0;
+    const uint32_t tb = toff32[2 * (h0 + cb + nz)];
+    // (dword k0 of the block's scratch = record k0 - 1; the slot's read on
+    // lane 0 alone, as a uniform one becomes a flat load of either space)
+    uint32_t rprev = recst[cb][min(k0, kRecPre - 1)];
+    wave_sync();
+    marks[wv][lane] = 0u;
+    if (sst - (uint32_t)f0 - 1u < 63u) marks[wv][sst - (uint32_t)f0] = desc;   // starts inside
+    wave_sync();
+    const uint32_t bd = max(wave_incl_max(marks[wv][lane]), cd);
+    const int bi = (int)(bd >> 16) - 1;        // the lane's block, of the workgroup's
+    const int k = f0 + lane - (int)(bd & 0xFFFFu);   // sequence index in the block
+    const int hb = h0 + bi;
+    uint32_t r = recst[bi][min(1 + k, kRecPre - 1)];
+    if (valid && 1 + k >= kRecPre)
+      r = reinterpret_cast<const uint32_t *>(wovf + bi * kOvf)[1 + k - kRecPre];
+    r = valid ? r : 0u;
+    asm volatile("" : "+v"(rprev));            // (keeps the two reads apart: ds_read, global_load)
+    if (lane == 0 && k0 >= kRecPre)
+      rprev = reinterpret_cast<const uint32_t *>(wovf + cb * kOvf)[k0 - kRecPre];
+    const int end_prev = k0 != 0 ? (int)(rprev >> 19) : 0;
+    // record = the sequence's match word: dist | M << 9 | (match start +
+    // M) << 19 (the literal tail: n << 19)
+    const int M = (int)((r >> 9) & 255u), D = (int)(r & 511u);
+    const int end = (int)(r >> 19);
+    const int cpos = end - M;
+    const uint32_t upv = dpp<0x138, 0xf, 0xf>((uint32_t)end);   // wave_shr:1
+    const int pend = k == 0 ? 0 : (lane == 0 ? end_prev : (int)upv);   // literal run start
+    const int L = cpos - pend;
+    const int rem = (L - 15) & 255;
+    const int le = L >= 15 ? (rem == 255 ? 2 : 1) : 0;         // literal-extension bytes
+    const int mx = (M - 4) & 255;
+    const bool mextW = M >= 4 && mx >= 15, mextS = M != 0 && mx >= 15;
+    const int bytes = valid ? 5 + le + L + (mextW ? 1 : 0) : 0;
+    const uint32_t inc = wave_incl_add((uint32_t)bytes);
+    // the round's first token, with no word from another wave: block cb
+    // starts here (its offset + 3), or ends in this round (the next block's
+    // offset less the bytes to its end); a block with neither in the round
+    // (> 64 records, none in text) sums its records before f0
+    const int tail = __builtin_amdgcn_readlane((int)inc, (cn - 1) & 63);
+    int first = rel + (int)tb + (nz ? -tail : 3);
+    if (nz & (cn > 64 ? 1 : 0)) {
+      int pre = 0, pe = 0;
+      for (int j0 = 0; j0 < k0; j0 += 64) {
+        const int j = j0 + lane;
+        const uint32_t q = j < k0 ? load_record(recst, wovf, cb, j) : 0u;
+        const uint32_t up = dpp<0x138, 0xf, 0xf>(q >> 19);
+        const int qb = j < k0 ? sequence_bytes(q, lane == 0 ? pe : (int)up) : 0;
+        pe = (int)lane63(q >> 19);
+        pre += (int)lane63(wave_incl_add((uint32_t)qb));
+      }
+      first = rel + (int)toff32[2 * (h0 + cb)] + 3 + pre;
+    }
+    const int o = first + 3 * (bi - cb) + (int)inc - bytes;       // the sequence's token
+    const int ib = o - 3;                                         // (k == 0) its block's header
+    const int ol = o + 3 + le;                                   // first literal byte
+    if (valid) {
+      const int tl = L >= 15 ? 15 : L;                            // LZ4.c:540
+      const int tm = M == 0 ? 0 : (M >= 19 ? 15 : mx);            // LZ4.c:542
+      const uint32_t ext = le == 0 ? 0u : (rem == 255 ? 255u : (uint32_t)rem);
+      const uint32_t SZ = (uint32_t)(5 + le + L + (mextS ? 1 : 0));   // LZ4.c:546-575
+      or_bytes(out32, o, (uint32_t)((tl << 4) | tm) | (SZ << 8) | (ext << 24));
+      or_bytes(out32, ol + L, (uint32_t)D | (mextW ? ((uint32_t)(mx - 15) & 255u) << 16 : 0u));
+      if (k == 0) {                                               // LZ4.c:417-419
+        const uint32_t bh = recst[hb - h0][0];
+        or_bytes(out32, ib, ((bh >> 16) & 255u) | ((((bh & 0xFFFFu) + 3u) & 0xFFFFu) << 8));
+      }
+    }
+    // literals (LZ4.c:388), flattened over the lanes: one aligned 16-byte
+    // image word per lane and pass, funnel-shifted out of five aligned
+    // staged input dwords and masked to the run (16-B words: half the
+    // passes of 8-B ones; two ds_or_b64 per word)
+    {
+      const int cw = valid && L > 0 ? ((ol + L - 1) >> 4) - (ol >> 4) + 1 : 0;
+      const uint32_t cinc = wave_incl_add((uint32_t)cw);
+      const int C = (int)lane63(cinc);
+      const int stw = (int)dpp<0x138, 0xf, 0xf>(cinc);
+      // the run, as its owning lanes use it: image word w = (ol >> 3) - stw + gw,
+      // stage byte of that word's first image byte xs = 8 w + (src - ol), and
+      // its bytes [ol, ol + L) of the image (two 16-bit fields per dword)
+      const int src = kStagePad + kBlk * (hb - h0) + pend;
+      const uint32_t rw = ((uint32_t)((ol >> 4) - stw) & 0xFFFFu) | ((uint32_t)(src - ol) << 16);
+      const uint32_t rb = (uint32_t)ol | ((uint32_t)(ol + L) << 16);
+      uint32_t carry = 0;                    // 1 + the last run owning a word so far
+      for (int w0 = 0; w0 < C; w0 += 64) {
+        wave_sync();
+        marks[wv][lane] = 0u;
+        if (cw > 0 && stw >= w0 && stw < w0 + 64) marks[wv][stw - w0] = (uint32_t)lane + 1u;
+        wave_sync();
+        const uint32_t k1 = max(wave_incl_max(marks[wv][lane]), carry);
+        carry = lane63(k1);
+        const int gw = w0 + lane;
+        const int kr = ((int)k1 - 1) & 63;   // the run owning word gw
+        const uint32_t kw = (uint32_t)__shfl((int)rw, kr, 64);
+        const uint32_t kb = (uint32_t)__shfl((int)rb, kr, 64);
+        if (gw < C) {
+          const int t = 16 * ((int)(int16_t)(kw & 0xFFFFu) + gw);  // image word's first byte
+          const int xs = t + ((int)kw >> 16);                      // its input bytes
+          const uint32_t *iw = reinterpret_cast<const uint32_t *>(stage + (xs & ~3));
+          const uint32_t d0 = iw[0], d1 = iw[1], d2 = iw[2], d3 = iw[3], d4 = iw[4];
+          const uint32_t sh = (uint32_t)xs & 3u;
+          const int lb = max((int)(kb & 0xFFFFu) - t, 0), hb = min((int)(kb >> 16) - t, 16);
+          const uint4 ml = pmask[lb], mh = pmask[hb];
+          const uint32_t v0 = __builtin_amdgcn_alignbyte(d1, d0, sh) & (ml.x ^ mh.x);
+          const uint32_t v1 = __builtin_amdgcn_alignbyte(d2, d1, sh) & (ml.y ^ mh.y);
+          const uint32_t v2 = __builtin_amdgcn_alignbyte(d3, d2, sh) & (ml.z ^ mh.z);
+          const uint32_t v3 = __builtin_amdgcn_alignbyte(d4, d3, sh) & (ml.w ^ mh.w);
+          atomicOr(reinterpret_cast<unsigned long long *>(img + t),
+                   (unsigned long long)v1 << 32 | v0);
+          atomicOr(reinterpret_cast<unsigned long long *>(img + t + 8),
+                   (unsigned long long)v3 << 32 | v2);
         }
-        const int k = f - sb;                      // sequence index in the block
-        const int hb = bl0 + bi;
-        const uint32_t *rp = reinterpret_cast<const uint32_t *>(wovf + (hb - h0) * kOvf);
-        const uint32_t r =
-            !valid ? 0u : (1 + k < kRecPre ? recst[hb - h0][1 + k] : rp[1 + k - kRecPre]);
-        // record = the sequence's match word: dist | M << 9 | (match start +
-        // M) << 19 (the literal tail: n << 19)
-        const int M = (int)((r >> 9) & 255u), D = (int)(r & 511u);
-        const int end = (int)(r >> 19);
-        const int cpos = end - M;
-        const uint32_t upv = dpp<0x138, 0xf, 0xf>((uint32_t)end);   // wave_shr:1
-        const int pend = k == 0 ? 0 : (lane == 0 ? end_prev : (int)upv);   // literal run start
-        end_prev = (int)lane63((uint32_t)end);
-        const int L = cpos - pend;
-        const int rem = (L - 15) & 255;
-        const int le = L >= 15 ? (rem == 255 ? 2 : 1) : 0;         // literal-extension bytes
-        const int mx = (M - 4) & 255;
-        const bool mextW = M >= 4 && mx >= 15, mextS = M != 0 && mx >= 15;
-        const int bytes = valid ? 5 + le + L + (mextW ? 1 : 0) : 0;
-        const uint32_t inc = wave_incl_add((uint32_t)bytes);
-        const int o = wcur + 3 * bi + (int)inc - bytes;               // the sequence's token
-        const int ib = o - 3;                                         // (k == 0) its block's header
-        const int ol = o + 3 + le;                                   // first literal byte
-        if (valid) {
-          const int tl = L >= 15 ? 15 : L;                            // LZ4.c:540
-          const int tm = M == 0 ? 0 : (M >= 19 ? 15 : mx);            // LZ4.c:542
-          const uint32_t ext = le == 0 ? 0u : (rem == 255 ? 255u : (uint32_t)rem);
-          const uint32_t SZ = (uint32_t)(5 + le + L + (mextS ? 1 : 0));   // LZ4.c:546-575
-          or_bytes(out32, o, (uint32_t)((tl << 4) | tm) | (SZ << 8) | (ext << 24));
-          or_bytes(out32, ol + L, (uint32_t)D | (mextW ? ((uint32_t)(mx - 15) & 255u) << 16 : 0u));
-          if (k == 0) {                                               // LZ4.c:417-419
-            const uint32_t bh = recst[hb - h0][0];
-            or_bytes(out32, ib, ((bh >> 16) & 255u) | ((((bh & 0xFFFFu) + 3u) & 0xFFFFu) << 8));
-          }
-        }
-        // literals (LZ4.c:388), flattened over the lanes: one aligned 16-byte
-        // image word per lane and pass, funnel-shifted out of five aligned
-        // staged input dwords and masked to the run (16-B words: half the
-        // passes of 8-B ones; two ds_or_b64 per word)
-        {
-          const int cw = valid && L > 0 ? ((ol + L - 1) >> 4) - (ol >> 4) + 1 : 0;
-          const uint32_t cinc = wave_incl_add((uint32_t)cw);
-          const int C = (int)lane63(cinc);
-          const int stw = (int)dpp<0x138, 0xf, 0xf>(cinc);
-          // the run, as its owning lanes use it: image word w = (ol >> 3) - stw + gw,
-          // stage byte of that word's first image byte xs = 8 w + (src - ol), and
-          // its bytes [ol, ol + L) of the image (two 16-bit fields per dword)
-          const int src = kStagePad + kBlk * (hb - h0) + pend;
-          const uint32_t rw = ((uint32_t)((ol >> 4) - stw) & 0xFFFFu) | ((uint32_t)(src - ol) << 16);
-          const uint32_t rb = (uint32_t)ol | ((uint32_t)(ol + L) << 16);
-          uint32_t carry = 0;                    // 1 + the last run owning a word so far
-          for (int w0 = 0; w0 < C; w0 += 64) {
-            wave_sync();
-            marks[wv][lane] = 0u;
-            if (cw > 0 && stw >= w0 && stw < w0 + 64) marks[wv][stw - w0] = (uint32_t)lane + 1u;
-            wave_sync();
-            const uint32_t k1 = max(wave_incl_max(marks[wv][lane]), carry);
-            carry = lane63(k1);
-            const int gw = w0 + lane;
-            const int kr = ((int)k1 - 1) & 63;   // the run owning word gw
-            const uint32_t kw = (uint32_t)__shfl((int)rw, kr, 64);
-            const uint32_t kb = (uint32_t)__shfl((int)rb, kr, 64);
-            if (gw < C) {
-              const int t = 16 * ((int)(int16_t)(kw & 0xFFFFu) + gw);  // image word's first byte
-              const int xs = t + ((int)kw >> 16);                      // its input bytes
-              const uint32_t *iw = reinterpret_cast<const uint32_t *>(stage + (xs & ~3));
-              const uint32_t d0 = iw[0], d1 = iw[1], d2 = iw[2], d3 = iw[3], d4 = iw[4];
-              const uint32_t sh = (uint32_t)xs & 3u;
-              const int lb = max((int)(kb & 0xFFFFu) - t, 0), hb = min((int)(kb >> 16) - t, 16);
-              const uint4 ml = pmask[lb], mh = pmask[hb];
-              const uint32_t v0 = __builtin_amdgcn_alignbyte(d1, d0, sh) & (ml.x ^ mh.x);
-              const uint32_t v1 = __builtin_amdgcn_alignbyte(d2, d1, sh) & (ml.y ^ mh.y);
-              const uint32_t v2 = __builtin_amdgcn_alignbyte(d3, d2, sh) & (ml.z ^ mh.z);
-              const uint32_t v3 = __builtin_amdgcn_alignbyte(d4, d3, sh) & (ml.w ^ mh.w);
-              atomicOr(reinterpret_cast<unsigned long long *>(img + t),
-                       (unsigned long long)v1 << 32 | v0);
-              atomicOr(reinterpret_cast<unsigned long long *>(img + t + 8),
-                       (unsigned long long)v3 << 32 | v2);
-            }
-          }
-        }
-        wcur += (int)lane63(inc);
       }
     }
   }

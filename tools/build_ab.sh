@@ -29,5 +29,5 @@ FLAGS="$(make -s print-HIPFLAGS) $EXTRA"
 $HIPCC $FLAGS -I lz4-jpeg_amd/csrc -c $D/$obj.hip -o $D/$obj.o
 $HIPCC $FLAGS -I lz4-jpeg_amd/csrc --cuda-device-only -S $D/$obj.hip -o - | grep -v __hip_cuid_ > tools/ab/${obj}_$2.s
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o tools/ab/$lib \
-  $D/$obj.o $(ls lz4-jpeg_amd/build/*.o | grep -v -e "/$obj.o" -e _seq.o -e _par.o -e png_io.o)
+  $D/$obj.o $(ls lz4-jpeg_amd/build/*.o | grep -v -e "/$obj.o" -e _seq.o -e _par.o -e _dec.o -e png_io.o)
 echo built tools/ab/$lib

@@ -1,9 +1,12 @@
-// jpegr_entropy_common.h -- what the entropy stage's encoders share: the
-// per-lane LDS columns, the reference's heap / tree / code build
-// (tree_codes and its sifts), the hashed encoder of one stream
-// (encode_stream) and the lane kernels' LDS layout.  jpegr_entropy.hip (the
-// slot encoder) and jpegr_stream_enc.hip (the encoder straight to a JPR1 /
-// JPT1 stream) each keep their own kernel shell around these.
+// jpegr_entropy_common.h -- the entropy stage's constants and what its
+// encoders share: the per-lane LDS columns, the reference's heap / tree / code
+// build (tree_codes and its sifts), the hashed encoder of one stream
+// (encode_stream) with its working set's layout, the lane kernels' LDS layout
+// and their walk (lane_rle_count, lane_heap_seed, lane_sequence).
+// jpegr_entropy.hip (the slot encoder) and jpegr_stream_enc.hip (the encoder
+// straight to a JPR1 / JPT1 stream) each keep their own kernel shell around
+// these: where the lanes leave, where the table goes, and everything after the
+// sequence pass.  The decoders' side is jpegr_decode_common.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -532,6 +535,19 @@ __device__ int encode_stream(const int16_t *__restrict__ zz, int n, const W &w,
 template <typename T>
 using GColT = Col<T>;
 
+// One working set of the hashed encoder (encode_stream<kFullCap, 2 * kFullCap>):
+// kEnd bytes at a 4-B aligned lb, global or LDS
+constexpr int kSymO = 0, kHashO = kSymO + 2 * kFullCap, kHeapO = kHashO + 2 * kFullCap;
+constexpr int kCodeO = (kHeapO + 2 * (kFullCap + 2) + 3) & ~3, kLenO = kCodeO + 4 * kFullCap;
+constexpr int kStkO = (kLenO + kFullCap + 1) & ~1, kEnd = kStkO + 2 * (kFullCap + 1);
+
+__device__ __forceinline__ Work<GColT> hashed_work(uint8_t *lb) {
+  return {{reinterpret_cast<int16_t *>(lb + kSymO), 1}, {lb + kHashO, 1},
+          {reinterpret_cast<uint16_t *>(lb + kHeapO), 1},
+          {reinterpret_cast<uint32_t *>(lb + kCodeO), 1}, {lb + kLenO, 1},
+          {reinterpret_cast<uint16_t *>(lb + kStkO), 1}};
+}
+
 // Scratch (d_scratch): per luma wave a list of its deferred streams (64
 // entries), then per luma wave a word deferred | overflowed << 8 (lanes).
 // The chroma kernel reads them (its even wave 2 v: luma wave v), so no
@@ -603,5 +619,177 @@ struct LaneWork {                                     // the arrays tree_codes u
   LCol<uint32_t> mrec;   // merged node m's record (the dead table's rows, before the codes)
   LCol<uint16_t> dep;    // (depth | leaf << 8) by DFS position (the dead heap's rows)
 };
+
+// ---- the lane encoders' walk: what entropy_encode_lane (slots) and
+// stream_encode_lane (a JPR1 / JPT1 stream) do alike, in the order they do it.
+// tabc, heap, sym: the lane's columns of LaneLds<N>'s tab, heap and sym rows.
+
+// What the RLE + count walk leaves beside the leaf ids: the distinct symbols
+// (clamped to Cap), the RLE ints and whether the stream is deferred
+struct LaneRle {
+  int U, R;
+  bool defer;
+};
+
+// RLE (JPEG.c:767-808) + frequencies (JPEG.c:864-886) of the N ints at zz:
+// run k ends at position i when i == N - 1 or the next int differs; it emits
+// (count, value).  Leaf ids in first-occurrence order; lid, per position:
+// (leaf_c + 1) | (leaf_v + 1) << 5, three positions per dword.
+template <int N>
+__device__ __forceinline__ LaneRle lane_rle_count(const int16_t *zz, uint8_t *tabc,
+                                                  uint8_t *heap, uint32_t (&lid)[(N + 2) / 3]) {
+  using L = LaneLds<N>;
+  constexpr int Cap = L::Cap, Keys = L::Keys, Off = L::Off;
+  // the stream: N int16 as N / 2 packed dwords (16-B loads)
+  uint32_t iw[N / 2];
+  {
+    const uint4 *src = reinterpret_cast<const uint4 *>(zz);
+#pragma unroll
+    for (int k = 0; k < N / 8; ++k) {
+      const uint4 q = src[k];
+      iw[4 * k] = q.x; iw[4 * k + 1] = q.y; iw[4 * k + 2] = q.z; iw[4 * k + 3] = q.w;
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < Keys / 4; ++r) *reinterpret_cast<uint32_t *>(tabc + r * (4 * kLanes)) = 0u;
+  auto val = [&](int i) { return (int)(int16_t)(iw[i >> 1] >> (16 * (i & 1))); };
+  auto tab_at = [&](int k) -> uint8_t & {
+    return *(tabc + (k >> 2) * (4 * kLanes) + (k & 3));
+  };
+  uint32_t ids = 0;                      // the ids of lid's dword under way
+  int U = 0, start = 0, R = 0;
+  bool defer = false;
+  // One exec region per position and no branch inside it: the stores are
+  // unconditional and idempotent (a known symbol rewrites its table entry and
+  // its symbol with the values they hold), and a count is a ds_add into the
+  // zeroed heap rows, which hold (symbol | count << 8) per leaf during the
+  // walk.  A stream that must be deferred runs on with clamped leaf ids over
+  // its own columns (the results are dropped).
+#pragma unroll
+  for (int r = 0; r < Cap / 2; ++r) *reinterpret_cast<uint32_t *>(heap + r * (4 * kLanes)) = 0u;
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const int v = val(i);
+    const bool end = i == N - 1 || val(i + 1 < N ? i + 1 : i) != v;
+    if (end) {
+      const int kc = i + 1 - start + Off;
+      start = i + 1;
+      const bool bad = (uint32_t)(v + Off) >= (uint32_t)Keys;
+      const int kv = bad ? kc : v + Off;
+      const int ec = tab_at(kc), ev = tab_at(kv);       // both reads in flight
+      const bool same = kv == kc;
+      const int lc = ec ? ec - 1 : U;
+      const int nu = U + (ec ? 0 : 1);
+      const int lv = same ? lc : (ev ? ev - 1 : nu);
+      const int nu2 = nu + ((same || ev) ? 0 : 1);
+      defer = defer || bad || nu2 > Cap;
+      const int lcw = min(lc, Cap - 1), lvw = min(lv, Cap - 1);
+      tab_at(kc) = (uint8_t)(lcw + 1);
+      tab_at(kv) = (uint8_t)(lvw + 1);
+      // leaf u's symbol and count: one u16 (symbol | count << 8) at half
+      // u & 1 of dword row u >> 1, so the store and the add share an address
+      uint8_t *const sc = heap + ((lcw >> 1) << 8), *const sv = heap + ((lvw >> 1) << 8);
+      const int hc = (lcw & 1) << 4, hv = (lvw & 1) << 4;
+      const bool fc = ec == 0, fv = !same && ev == 0;    // first occurrences
+      const uint32_t ac = (fc ? (uint32_t)(uint8_t)(kc - Off) : 0u) + ((same ? 2u : 1u) << 8);
+      const uint32_t av = (fv ? (uint32_t)(uint8_t)(kv - Off) : 0u) + ((same ? 0u : 1u) << 8);
+      atomicAdd(reinterpret_cast<uint32_t *>(sc), ac << hc);
+      atomicAdd(reinterpret_cast<uint32_t *>(sv), av << hv);
+      U = min(nu2, Cap);
+      R += 2;                                         // the run's (count, value)
+      ids |= (uint32_t)((lcw + 1) | ((lvw + 1) << 5)) << (10 * (i % 3));
+    }
+    if (i % 3 == 2 || i == N - 1) {
+      lid[i / 3] = ids;
+      ids = 0;
+    }
+  }
+  return {U, R, defer};
+}
+
+// The walk's (symbol | count << 8) per leaf -> the symbols (i8, 4 per dword),
+// the heap entries (count << 8 | leaf at slot leaf + 1) and, in registers,
+// h0: heap entry u's initial value, count << 8 | u (tree_codes)
+template <int N>
+__device__ __forceinline__ void lane_heap_seed(uint8_t *heap, uint8_t *sym,
+                                               uint32_t (&h0)[LaneLds<N>::Cap]) {
+  using L = LaneLds<N>;
+  constexpr int Cap = L::Cap;
+  auto row = [&](int r) { return reinterpret_cast<uint32_t *>(heap + r * (4 * kLanes)); };
+  uint32_t sc[Cap / 2];
+#pragma unroll
+  for (int k = 0; k < Cap / 2; ++k) sc[k] = *row(k);
+#pragma unroll
+  for (int u = 0; u < Cap; ++u) h0[u] = ((sc[u >> 1] >> (16 * (u & 1))) & 0xFF00u) | (uint32_t)u;
+#pragma unroll
+  for (int j = 0; j < Cap / 4; ++j)
+    *reinterpret_cast<uint32_t *>(sym + j * (4 * kLanes)) =
+        __builtin_amdgcn_perm(sc[2 * j + 1], sc[2 * j], 0x06040200u);
+  if constexpr (L::Wide) {
+    // slot s (leaf s - 1) is row s
+#pragma unroll
+    for (int u = 0; u < Cap; ++u)
+      *row(u + 1) = ((sc[u >> 1] >> (16 * (u & 1))) & 0xFF00u) | (uint32_t)u;
+  } else {
+#pragma unroll
+    for (int r = 0; r < (Cap + 2) / 2; ++r) {
+      // slot 2r: leaf 2r - 1 (count: byte 3 of sc[r - 1]); slot 2r + 1: leaf 2r (byte 1 of sc[r])
+      const uint32_t lo = r > 0 ? (sc[r - 1] >> 16) & 0xFF00u : 0u;
+      const uint32_t hi = r < Cap / 2 ? (sc[r] & 0xFF00u) << 16 : 0u;
+      *row(r) = lo | hi | (uint32_t)(r > 0 ? 2 * r - 1 : 0) | (uint32_t)(2 * r) << 16;
+    }
+  }
+}
+
+// The encoded sequence, MSB-first (JPEG.c:993-1007), from bit pos0 of the
+// lane's bit rows at brow (row r at brow + 256 r): the bits_cap / 32 rows of
+// the slot, then kSpill rows (>= 2) that take what follows pos0 and the bits
+// of a stream that overflows its slot.  Returns the position past the last bit.
+// A leaf's code word is its code left-aligned with its length in the low
+// 5 bits (codez: the zero row, then the codes, so id 0 reads a length-0
+// code); the reads do not depend on the bit position, so each group of kG
+// positions' code words is read while the previous group is placed.  Each
+// code is or-ed into the lane's zeroed bit rows at its bit position (two
+// ds_or: the word it starts in and the next).  No exec branch per code: the
+// accumulator form stored each completed word under one.
+template <int N, int kSpill>
+__device__ __forceinline__ int lane_sequence(const uint32_t (&lid)[(N + 2) / 3],
+                                             const LCol<uint32_t> codez, uint8_t *brow, int pos0) {
+  constexpr int nwords = N / 2;                       // bits_cap / 32
+  auto bit_row = [&](int r) { return reinterpret_cast<uint32_t *>(brow + r * (4 * kLanes)); };
+  codez[0] = 0u;
+#pragma unroll
+  for (int r = 0; r < nwords + kSpill; ++r) *bit_row(r) = 0u;
+  int pos = pos0;
+  constexpr int kG = 4;
+  static_assert(N % kG == 0, "whole groups");
+  auto ident = [&](int i, int h) {                    // leaf + 1 of emission h at position i, 0: none
+    return (lid[i / 3] >> (10 * (i % 3) + 5 * h)) & 31u;
+  };
+  auto fetch = [&](int g, uint32_t (&cw)[2 * kG]) {
+#pragma unroll
+    for (int j = 0; j < 2 * kG; ++j) {
+      cw[j] = codez[(int)ident(g * kG + j / 2, j & 1)];
+    }
+  };
+  uint32_t cur[2 * kG], nxt[2 * kG];
+  fetch(0, nxt);
+#pragma unroll
+  for (int g = 0; g < N / kG; ++g) {
+#pragma unroll
+    for (int j = 0; j < 2 * kG; ++j) cur[j] = nxt[j];
+    if (g + 1 < N / kG) fetch(g + 1, nxt);
+#pragma unroll
+    for (int j = 0; j < 2 * kG; ++j) {
+      const uint32_t al = cur[j] & ~31u;
+      const uint32_t o = (uint32_t)pos & 31u;
+      uint32_t *const r0 = bit_row(min(pos >> 5, nwords + kSpill - 2));
+      atomicOr(r0, al >> o);
+      atomicOr(r0 + kLanes, __builtin_amdgcn_alignbit(al, 0u, o));   // (o = 0: none)
+      pos += (int)(cur[j] & 31u);
+    }
+  }
+  return pos;
+}
 
 }  // namespace

@@ -6,8 +6,9 @@
 //   jps_init           the call's own first launch: bump counters and result
 //                      words to 0
 //   stream_encode_lane jpegr_entropy.hip's lane-per-stream kernels (luma,
-//                      then chroma with the deferred streams; the shared parts
-//                      in jpegr_entropy_common.h) with another sink: a lane's
+//                      then chroma with the deferred streams; the walk itself
+//                      -- RLE + counts, heap seed, tree, sequence pass -- is
+//                      jpegr_entropy_common.h's) with another sink: a lane's
 //                      finished stream -- header, table in the format's coding,
 //                      bit bytes -- lies in its LDS column as whole dwords; a
 //                      wave scan of the dword counts and one atomicAdd per wave
@@ -91,12 +92,9 @@ __global__ void jps_init(uint64_t *__restrict__ ctrl, uint64_t *__restrict__ res
   if (threadIdx.x < 2) result[threadIdx.x] = 0;
 }
 
-// One working set of the hashed encoder (jpegr_entropy.hip's layout) and,
-// behind it, what the slot encoder writes to global slots: the stream's bits,
-// table and meta word.
-constexpr int kSymO = 0, kHashO = kSymO + 2 * kFullCap, kHeapO = kHashO + 2 * kFullCap;
-constexpr int kCodeO = (kHeapO + 2 * (kFullCap + 2) + 3) & ~3, kLenO = kCodeO + 4 * kFullCap;
-constexpr int kStkO = (kLenO + kFullCap + 1) & ~1, kEnd = kStkO + 2 * (kFullCap + 1);
+// One working set of the hashed encoder (jpegr_entropy_common.h) and, behind
+// it, what the slot encoder writes to global slots: the stream's bits, table
+// and meta word.
 constexpr int kBitsO = (kEnd + 3) & ~3, kTabO = kBitsO + 128, kMetaO = kTabO + 4 * kFullCap;
 constexpr int kSetB = (kMetaO + 4 + 15) & ~15;          // 16-B aligned
 
@@ -109,10 +107,7 @@ struct Hashed {
 
 __device__ __forceinline__ Hashed hashed_encode(const int16_t *__restrict__ coef, size_t t, int cc,
                                                 uint8_t *lb, bool tight) {
-  const Work<GColT> ws{{reinterpret_cast<int16_t *>(lb + kSymO), 1}, {lb + kHashO, 1},
-                       {reinterpret_cast<uint16_t *>(lb + kHeapO), 1},
-                       {reinterpret_cast<uint32_t *>(lb + kCodeO), 1}, {lb + kLenO, 1},
-                       {reinterpret_cast<uint16_t *>(lb + kStkO), 1}};
+  const Work<GColT> ws = hashed_work(lb);
   uint32_t *const stab = reinterpret_cast<uint32_t *>(lb + kTabO);
   Hashed e;
   e.rc = encode_stream<kFullCap, 2 * kFullCap>(coef + t * 128 + coef_off(cc), stream_len(cc), ws,
@@ -193,7 +188,7 @@ template <bool kLuma, bool kTight>
 __global__ __launch_bounds__(kLanes) void stream_encode_lane(const EncArgs a) {
   constexpr int N = kLuma ? 64 : 32;
   using L = LaneLds<N>;
-  constexpr int Cap = L::Cap, Keys = L::Keys, Off = L::Off;
+  constexpr int Cap = L::Cap;
   __shared__ L S;
   const int lane = threadIdx.x;
   const size_t bx = a.wg_base + blockIdx.x;
@@ -218,66 +213,11 @@ __global__ __launch_bounds__(kLanes) void stream_encode_lane(const EncArgs a) {
                             {colp(&S.tab[L::CodeRow][0])}, {colp(&S.tab[0][0])},
                             {colp(&S.heap[0][0])}};
 
-  // the stream: N int16 as N / 2 packed dwords (16-B loads)
-  uint32_t iw[N / 2];
-  {
-    const uint4 *src = reinterpret_cast<const uint4 *>(a.coef + tl * 128 + coef_off(c));
-#pragma unroll
-    for (int k = 0; k < N / 8; ++k) {
-      const uint4 q = src[k];
-      iw[4 * k] = q.x; iw[4 * k + 1] = q.y; iw[4 * k + 2] = q.z; iw[4 * k + 3] = q.w;
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < Keys / 4; ++r) *reinterpret_cast<uint32_t *>(tabc + r * (4 * kLanes)) = 0u;
-  auto val = [&](int i) { return (int)(int16_t)(iw[i >> 1] >> (16 * (i & 1))); };
-  auto tab_at = [&](int k) -> uint8_t & {
-    return *(tabc + (k >> 2) * (4 * kLanes) + (k & 3));
-  };
-  auto row = [&](int r) {                            // dword row r of the heap rows
-    return reinterpret_cast<uint32_t *>(w.heap.p + r * (4 * kLanes));
-  };
-
   // ---- RLE (JPEG.c:767-808) + frequencies (JPEG.c:864-886) ------------------
   uint32_t lid[(N + 2) / 3];             // per position: (leaf_c + 1) | (leaf_v + 1) << 5
-#pragma unroll
-  for (int j = 0; j < (N + 2) / 3; ++j) lid[j] = 0;
-  int U = 0, start = 0, R = 0;
-  bool defer = false;
-#pragma unroll
-  for (int r = 0; r < Cap / 2; ++r) *row(r) = 0u;
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    const int v = val(i);
-    const bool end = i == N - 1 || val(i + 1 < N ? i + 1 : i) != v;
-    if (end) {
-      const int kc = i + 1 - start + Off;
-      start = i + 1;
-      const bool bad = (uint32_t)(v + Off) >= (uint32_t)Keys;
-      const int kv = bad ? kc : v + Off;
-      const int ec = tab_at(kc), ev = tab_at(kv);       // both reads in flight
-      const bool same = kv == kc;
-      const int lc = ec ? ec - 1 : U;
-      const int nu = U + (ec ? 0 : 1);
-      const int lv2 = same ? lc : (ev ? ev - 1 : nu);
-      const int nu2 = nu + ((same || ev) ? 0 : 1);
-      defer = defer || bad || nu2 > Cap;
-      const int lcw = min(lc, Cap - 1), lvw = min(lv2, Cap - 1);
-      tab_at(kc) = (uint8_t)(lcw + 1);
-      tab_at(kv) = (uint8_t)(lvw + 1);
-      uint8_t *const sc = w.heap.p + ((lcw >> 1) << 8), *const sv = w.heap.p + ((lvw >> 1) << 8);
-      const int hc = (lcw & 1) << 4, hv = (lvw & 1) << 4;
-      const bool fc = ec == 0, fv = !same && ev == 0;    // first occurrences
-      const uint32_t ac = (fc ? (uint32_t)(uint8_t)(kc - Off) : 0u) + ((same ? 2u : 1u) << 8);
-      const uint32_t av = (fv ? (uint32_t)(uint8_t)(kv - Off) : 0u) + ((same ? 0u : 1u) << 8);
-      atomicAdd(reinterpret_cast<uint32_t *>(sc), ac << hc);
-      atomicAdd(reinterpret_cast<uint32_t *>(sv), av << hv);
-      U = min(nu2, Cap);
-      R += 2;                                         // the run's (count, value)
-      lid[i / 3] |= (uint32_t)((lcw + 1) | ((lvw + 1) << 5)) << (10 * (i % 3));
-    }
-  }
-  defer = defer && !skip;
+  const LaneRle rl = lane_rle_count<N>(a.coef + tl * 128 + coef_off(c), tabc, w.heap.p, lid);
+  const int U = rl.U, R = rl.R;
+  const bool defer = rl.defer && !skip;
   const uint64_t dm = __ballot(defer);                // the wave's deferred lanes
   if constexpr (kLuma) {
     // the chroma kernel's even wave 2 lv encodes them: the lane numbers
@@ -291,29 +231,7 @@ __global__ __launch_bounds__(kLanes) void stream_encode_lane(const EncArgs a) {
   bool over = false;
   if (!defer && !skip) {
     uint32_t h0[Cap];                                   // heap entry u: count << 8 | u
-    {
-      uint32_t sc[Cap / 2];
-#pragma unroll
-      for (int k = 0; k < Cap / 2; ++k) sc[k] = *row(k);
-#pragma unroll
-      for (int u = 0; u < Cap; ++u) h0[u] = ((sc[u >> 1] >> (16 * (u & 1))) & 0xFF00u) | (uint32_t)u;
-#pragma unroll
-      for (int j = 0; j < Cap / 4; ++j)
-        *reinterpret_cast<uint32_t *>(w.sym.p + j * (4 * kLanes)) =
-            __builtin_amdgcn_perm(sc[2 * j + 1], sc[2 * j], 0x06040200u);
-      if constexpr (L::Wide) {
-#pragma unroll
-        for (int u = 0; u < Cap; ++u)
-          *row(u + 1) = ((sc[u >> 1] >> (16 * (u & 1))) & 0xFF00u) | (uint32_t)u;
-      } else {
-#pragma unroll
-        for (int r = 0; r < (Cap + 2) / 2; ++r) {
-          const uint32_t lo = r > 0 ? (sc[r - 1] >> 16) & 0xFF00u : 0u;
-          const uint32_t hi = r < Cap / 2 ? (sc[r] & 0xFF00u) << 16 : 0u;
-          *row(r) = lo | hi | (uint32_t)(r > 0 ? 2 * r - 1 : 0) | (uint32_t)(2 * r) << 16;
-        }
-      }
-    }
+    lane_heap_seed<N>(w.heap.p, w.sym.p, h0);
 
     // ---- heap, tree and codes (JPEG.c:913-983): the table into registers ------
     uint32_t tbl[Cap];
@@ -335,45 +253,12 @@ __global__ __launch_bounds__(kLanes) void stream_encode_lane(const EncArgs a) {
     constexpr int BitRow = L::CodeRow + Cap;
     // rows 0 .. nwords hold the slot's bits behind up to 3 B of phase; two
     // spill rows take the bits of a stream that overflows its slot
-    static_assert(BitRow + nwords + 3 <= Keys / 4 + L::HeapRows + Cap / 4 &&
+    static_assert(BitRow + nwords + 3 <= L::Keys / 4 + L::HeapRows + Cap / 4 &&
                       offsetof(L, heap) == sizeof(S.tab) && offsetof(L, sym) == offsetof(L, heap) + sizeof(S.heap),
                   "the bit rows fit the dead rows past the codes");
     static_assert(1 + (3 * Cap + 3) / 4 <= BitRow, "header and table fit the rows before the bits");
     uint8_t *const brow = reinterpret_cast<uint8_t *>(&S) + BitRow * (4 * kLanes) + 4 * lane;
-    auto bit_row = [&](int r) { return reinterpret_cast<uint32_t *>(brow + r * (4 * kLanes)); };
-    codez[0] = 0u;
-#pragma unroll
-    for (int r = 0; r < nwords + 3; ++r) *bit_row(r) = 0u;
-    int pos = (int)(8u * ph);
-    constexpr int kG = 4;
-    static_assert(N % kG == 0, "whole groups");
-    auto ident = [&](int i, int h) {                    // leaf + 1 of emission h at position i, 0: none
-      return (lid[i / 3] >> (10 * (i % 3) + 5 * h)) & 31u;
-    };
-    auto fetch = [&](int g, uint32_t (&cw)[2 * kG]) {
-#pragma unroll
-      for (int j = 0; j < 2 * kG; ++j) {
-        cw[j] = codez[(int)ident(g * kG + j / 2, j & 1)];
-      }
-    };
-    uint32_t cur[2 * kG], nxt[2 * kG];
-    fetch(0, nxt);
-#pragma unroll
-    for (int g = 0; g < N / kG; ++g) {
-#pragma unroll
-      for (int j = 0; j < 2 * kG; ++j) cur[j] = nxt[j];
-      if (g + 1 < N / kG) fetch(g + 1, nxt);
-#pragma unroll
-      for (int j = 0; j < 2 * kG; ++j) {
-        const uint32_t al = cur[j] & ~31u;
-        const uint32_t o = (uint32_t)pos & 31u;
-        uint32_t *const r0 = bit_row(min(pos >> 5, nwords + 1));
-        atomicOr(r0, al >> o);
-        atomicOr(r0 + kLanes, __builtin_amdgcn_alignbit(al, 0u, o));   // (o = 0: none)
-        pos += (int)(cur[j] & 31u);
-      }
-    }
-    const int nbits = pos - (int)(8u * ph);
+    const int nbits = lane_sequence<N, 3>(lid, codez, brow, (int)(8u * ph)) - (int)(8u * ph);
     if (nbits > ref_bits_max(c)) over = true;           // char sequence[1024] / [512]
     const uint32_t nb = (uint32_t)min(nbits, bits_cap(c));   // what the slot would hold
 

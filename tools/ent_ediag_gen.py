@@ -1,9 +1,12 @@
 """Make a phase-stamp diag source of jpegr_entropy.hip (tools only):
     python3 tools/ent_ediag_gen.py in.hip out.hip
 s_memtime stamps (lane 0 of each encode wave) into g_eph[kernel][wave][k]:
-0 start, 1 before the RLE, 2 after it, 3 before tree_codes, 4 after it,
-5 after the sequence bits, 6 after the meta word; read with jpegr_eph_read
-(tools/ent_ephase.py)."""
+0 start, 1 before the RLE (lane_rle_count: the ints' loads and the table's
+zeroing are inside it, so they count to the RLE now, not to the start), 2
+after it, 3 before tree_codes (after lane_heap_seed), 4 after it, 5 after the
+sequence bits (lane_sequence), 6 after the meta word; read with
+jpegr_eph_read (tools/ent_ephase.py).  The anchors are lines of the kernel
+shell; the walk between them is jpegr_entropy_common.h's."""
 import sys
 
 src = open(sys.argv[1]).read()
@@ -26,7 +29,7 @@ rep("  uint64_t dm = 0;                                    // (luma) the wave's 
     ST % 2 + "  uint64_t dm = 0;                                    // (luma) the wave's deferred lanes")
 rep('    bool over = tree_codes<Cap>(w, U, table + tile * kTablePerTile + bits_off(c), h0);',
     ST % 3 + '    bool over = tree_codes<Cap>(w, U, table + tile * kTablePerTile + bits_off(c), h0);\n' + ST % 4)
-rep('    const int nbits = pos;', ST % 5 + '    const int nbits = pos;')
+rep('    if (nbits > ref_bits_max(c)) over = true;', ST % 5 + '    if (nbits > ref_bits_max(c)) over = true;')
 rep('''    } else if (over) {
       atomicAdd(&status[0], 1u);
     }

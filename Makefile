@@ -6,6 +6,8 @@
 #                                         also as LZ4_seq.exe / JPEG_seq.exe
 #   lz4-jpeg_amd/bin/JPEG_dec             coefficients.jpr -> PNG (also JPEG_dec.exe)
 #   oracle/liboracle.so (+ oracle/_ref)   test-only CPU checker
+#   lz4-jpeg_amd/build/liblz4r_chunk12.so test-only: the compressor alone, cut into
+#                                         launch chunks of 2^12 blocks
 HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
 CC      ?= gcc
@@ -24,6 +26,13 @@ LZ4R_HIPFLAGS := -mllvm -amdgpu-sched-strategy=max-ilp
 LZ4R_GPUDEC_HIPFLAGS := -mllvm -amdgpu-sched-strategy=max-memory-clause
 CFLAGS_HOST := -O2 -fPIC -Wall -std=gnu11 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include
 LIB     := $(PKG)/lz4jpeg/liblz4jpeg.so
+# test-only variant of lz4r.hip (self-contained: the compressor and its C ABI)
+# with launch chunks of 2^12 blocks instead of 2^24, so that tests of a few MB
+# cross chunk boundaries (tests/test_gpu_lz4_chunks.py); 2^12 = kPart, the
+# smallest chunk the source accepts.  The product's flags plus the one define.
+CHUNK12_LIB := $(B)/liblz4r_chunk12.so
+CHUNK12_DEFINE := -DLZ4R_CHUNK_LOG2=12
+CHUNK12_HIPFLAGS = $(HIPFLAGS) $(LZ4R_HIPFLAGS) $(CHUNK12_DEFINE)
 HDRS    := include/lz4r.h include/jpegr.h include/lz4jpeg_compat.h include/lz4jpeg_synth.h \
            $(CSRC)/jpeg_tables.h \
            $(CSRC)/wave64.h $(CSRC)/lz4r_prof.h $(CSRC)/lz4r_layout.h $(CSRC)/lz4r_tile_lds.h \
@@ -36,7 +45,7 @@ OBJS    := $(B)/lz4r.o $(B)/lz4r_gpudec.o $(B)/jpegr.o $(B)/jpegr_blocks.o $(B)/
            $(B)/synth.o $(B)/synth_dev.o \
            $(B)/lz4r_decode.o $(B)/compat.o $(B)/compat_lz4.o
 
-all: lib bin oracle tools
+all: lib bin oracle tools chunk12
 
 lib: $(LIB)
 
@@ -60,6 +69,12 @@ $(B)/%.o: $(HOST)/%.c $(HDRS) $(HOST)/lzj_host.h
 
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
+
+chunk12: $(CHUNK12_LIB)
+
+$(CHUNK12_LIB): $(CSRC)/lz4r.hip $(HDRS)
+	@mkdir -p $(B)
+	$(HIPCC) $(CHUNK12_HIPFLAGS) -shared -o $@ $<
 
 # executables link the objects statically (no liblz4jpeg.so lookup at run time)
 $(BIN)/LZ4_seq: $(B)/lz4_seq.o $(OBJS)
@@ -131,7 +146,7 @@ clean:
 	rm -rf $(B) $(BIN) $(LIB) build
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib bin oracle tools sanitize clean
+.PHONY: all lib bin oracle tools chunk12 sanitize clean
 
 # `make -s print-HIPFLAGS`: a variable's value (tests/test_isa.py builds with the product flags)
 print-%:

@@ -65,6 +65,12 @@ void lz4r_ctx_destroy(lz4r_ctx *ctx);
 size_t lz4r_compress_bound(size_t n);
 size_t lz4r_nblocks(size_t n);
 
+/* Blocks per launch chunk of this build of the library: 2^24 in the product
+ * (a longer call is cut into that many blocks per pass of the kernels, see
+ * above); a test build compiled with -DLZ4R_CHUNK_LOG2=k reports 2^k, so a
+ * test can tell that its input really crosses chunks.  Read-only. */
+size_t lz4r_launch_chunk_blocks(void);
+
 /* Compress n bytes at d_in (device) into d_out (device, cap bytes) on
  * `stream`, then synchronise it and return the compressed length in
  * *out_len.  Frame header included.  Bytes equal lz4_encode()'s

@@ -296,6 +296,8 @@ void lz4r_ctx_destroy(lz4r_ctx *c) {
 
 size_t lz4r_nblocks(size_t n) { return (n + kBlk - 1) / kBlk; }
 
+size_t lz4r_launch_chunk_blocks(void) { return kChunk; }
+
 size_t lz4r_compress_bound(size_t n) { return 1 + lz4r_nblocks(n) * (size_t)LZ4R_BLOCK_BOUND; }
 
 int lz4r_compress_async(lz4r_ctx *c, const void *d_in, size_t n, void *d_out, size_t cap,

@@ -21,6 +21,7 @@ SIGNATURES = [
     ("lz4r_ctx_destroy", None, [_vp]),
     ("lz4r_compress_bound", _c_size, [_c_size]),
     ("lz4r_nblocks", _c_size, [_c_size]),
+    ("lz4r_launch_chunk_blocks", _c_size, []),
     ("lz4r_compress_device", _i, [_vp, _vp, _c_size, _vp, _c_size, ctypes.POINTER(_c_size), _vp]),
     ("lz4r_compress_async", _i, [_vp, _vp, _c_size, _vp, _c_size, _vp, _vp]),
     ("lz4r_compress_segment_async", _i, [_vp, _vp, _c_size, _vp, _c_size, _vp, _i, _vp]),

@@ -53,6 +53,33 @@ static unsigned lz4o_find_longest_match(const uint8_t *blk, size_t n, size_t p,
     return 0;
 }
 
+/* find_longest_match (LZ4.c:290-323) at positions [p0, p1) of ONE block of any
+ * length n, as the batch match finders of the HIP path report it
+ * (include/lz4r.h): out[p - p0] = len | dist << 16 with len NOT truncated to
+ * uint8_t, or 0 when len < MIN_MATCH_LENGTH.  Sources i in
+ * [max(0, p - WINDOW_SIZE), p) (LZ4.c:295-297), the length capped at
+ * MAX_MATCH_LENGTH and clamped at the block end, strict '>' (LZ4.c:307: the
+ * smallest source still inside the window wins ties).  The per-block finder
+ * is this function on each 300-byte piece with the piece's own length. */
+void lz4o_matches(const uint8_t *blk, size_t n, size_t p0, size_t p1, uint32_t *out)
+{
+    for (size_t p = p0; p < p1 && p < n; ++p) {
+        size_t best = 0, best_dist = 0;
+        size_t start = (p >= LZ4O_WINDOW) ? p - LZ4O_WINDOW : 0;
+        for (size_t i = start; i < p; ++i) {
+            size_t l = 0;
+            while (l < LZ4O_MAX_MATCH && p + l < n && blk[i + l] == blk[p + l])
+                l++;
+            if (l > best) {
+                best = l;
+                best_dist = p - i;
+            }
+        }
+        out[p - p0] = best >= LZ4O_MIN_MATCH
+                          ? (uint32_t)best | (uint32_t)best_dist << 16 : 0u;
+    }
+}
+
 /* byte count of the literal-length extension, LZ4.c:548-560 / 372-386 */
 static unsigned litext_len(size_t L)
 {

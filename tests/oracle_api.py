@@ -28,6 +28,8 @@ class Oracle:
         L.lz4o_decompress.restype = _sz
         L.lz4o_decompress.argtypes = [_vp, _sz, _vp, _sz, _sz]
         L.lz4o_block_bound.restype = _sz
+        L.lz4o_matches.restype = None
+        L.lz4o_matches.argtypes = [_vp, _sz, _sz, _sz, _vp]
         for f in ("jo_encode_image", "jo_dct_raw_image"):
             getattr(L, f).argtypes = [_vp, ctypes.c_int, ctypes.c_int, _vp]
         L.jo_encode_image_parallel.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]
@@ -51,6 +53,30 @@ class Oracle:
         n = self.L.lz4o_encode_blocks(b.ctypes.data_as(_vp), b.size, b0, b1,
                                       out.ctypes.data_as(_vp))
         return out[:n].tobytes()
+
+    def lz4_matches(self, data, p0=0, p1=None):
+        """find_longest_match at positions [p0, p1) of `data` taken as ONE
+        block of its own length: uint32 len | dist << 16 (len not truncated),
+        0 below 4 (lz4o_matches)."""
+        b = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+        p1 = b.size if p1 is None else p1
+        assert 0 <= p0 <= p1 <= b.size
+        out = np.zeros(p1 - p0, np.uint32)
+        self.L.lz4o_matches(b.ctypes.data_as(_vp), b.size, p0, p1, out.ctypes.data_as(_vp))
+        return out
+
+    def lz4_block_matches(self, data):
+        """The block form: lz4_matches of every 300-byte piece with the
+        piece's own length, concatenated (what lz4r_block_matches_device
+        reports)."""
+        b = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8)
+                                 if not isinstance(data, np.ndarray) else data)
+        out = np.zeros(b.size, np.uint32)
+        for o in range(0, b.size, 300):
+            piece = b[o:o + 300]
+            self.L.lz4o_matches(piece.ctypes.data_as(_vp), piece.size, 0, piece.size,
+                                out[o:].ctypes.data_as(_vp))
+        return out
 
     def lz4_decompress(self, comp, nblocks, cap):
         c = np.frombuffer(bytes(comp), dtype=np.uint8)

@@ -13,72 +13,28 @@ import pytest
 
 import entropy_inputs as E
 import jpr_format as J
+from jpr_gpu_lib import (SENTINEL, U64, crafted, crafted_jpr, encoded, encoded_jpr, gpu_decode,
+                         jpr_mutations, pack_scratch)
 
 pytestmark = pytest.mark.gpu
 
-U64 = (1 << 64) - 1
-SENTINEL = 12345
-PAD = 64                                 # int16 either side of the coefficients (128 B)
+
+def _crafted(oracle):
+    """(expected coefficients, the JPR1 stream, dims) of the crafted batch."""
+    _, want, dims = crafted(oracle)
+    return want, crafted_jpr(oracle), dims
 
 
-def gpu_decode(data, in_len, dims, tile0=0, ntile=None, tail=b"", lead=0):
-    """(coefficients [ntile, 128], [implied, verdict, rejected] as unsigned) of
-    the direct decode of data[:in_len], which sits `lead` bytes into its
-    buffer and is followed there by data[in_len:] + tail.  d_coef is a 16-B
-    aligned view inside a sentinel-filled tensor whose sentinels are checked;
-    d_result starts as garbage."""
-    import torch
-    from lz4jpeg import jpeg
-    w, h, nimg = dims
-    nt = J.ntiles_of(w, h, nimg)
-    ntile = nt - tile0 if ntile is None else ntile
-    buf = torch.from_numpy(np.frombuffer(bytes(lead) + bytes(data) + bytes(tail), np.uint8).copy()).cuda()
-    big = torch.full((ntile * 128 + 2 * PAD,), SENTINEL, dtype=torch.int16, device="cuda")
-    view = big[PAD:PAD + ntile * 128]
-    assert view.data_ptr() % 16 == 0
-    res = torch.full((3,), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64, device="cuda")
-    out, r = jpeg.decode_stream_device(buf[lead:], in_len, w, h, nimg, tile0, ntile, d_coef=view,
-                                       d_result=res)
-    torch.cuda.synchronize()
-    assert out.data_ptr() == view.data_ptr() and r.data_ptr() == res.data_ptr()
-    host = big.cpu().numpy()
-    assert (host[:PAD] == SENTINEL).all() and (host[-PAD:] == SENTINEL).all()
-    return host[PAD:-PAD].reshape(ntile, 128).copy(), [int(x) & U64 for x in res.cpu().tolist()]
-
-
-@functools.lru_cache(maxsize=None)
-def crafted(oracle):
-    cb = E.crafted_batch(oracle)
-    bits, meta, table, want = E.pack(cb.streams)
-    nt = len(cb.streams)
-    assert nt == 704
-    return want, J.pack(bits, meta, table, 8 * nt, 8, 1), (8 * nt, 8, 1)
-
-
-@functools.lru_cache(maxsize=None)
-def encoded(nt, w=None, h=None, nimg=1):
-    """nt tiles of rng.integers(-3, 4) coefficients through Entropy.encode
-    (test_gpu_jpeg_pack.encoded): (coefficients, the restatement's packing of
-    the slots, dims)."""
-    import torch
-    from lz4jpeg import jpeg
-    w, h = (8 * nt, 8) if w is None else (w, h)
-    assert J.ntiles_of(w, h, nimg) == nt
-    coef = np.random.default_rng(1000 + nt).integers(-3, 4, size=(nt, 128)).astype(np.int16)
-    ent = jpeg.Entropy(nt)
-    ent.encode(torch.from_numpy(coef.reshape(-1)).cuda())
-    torch.cuda.synchronize()
-    assert int(ent.status[0].item()) == 0
-    arrays = (ent.bits.cpu().numpy().reshape(nt, 256),
-              ent.meta.cpu().numpy().view(np.uint32).reshape(nt, 3),
-              ent.table.cpu().numpy().view(np.uint32).reshape(nt, 256))
-    return coef, J.pack(*arrays, w, h, nimg), (w, h, nimg)
+def _encoded(*args):
+    """(coefficients, the JPR1 stream, dims) of jpr_gpu_lib.encoded(*args)."""
+    _, coef, dims = encoded(*args)
+    return coef, encoded_jpr(*args), dims
 
 
 # ---- crafted batch ---------------------------------------------------------------
 
 def test_crafted_whole(gpu, oracle):
-    want, data, dims = crafted(oracle)
+    want, data, dims = _crafted(oracle)
     got, res = gpu_decode(data, len(data), dims)
     assert res == [len(data), U64, 0]
     assert np.array_equal(got, want)
@@ -86,7 +42,7 @@ def test_crafted_whole(gpu, oracle):
 
 @pytest.mark.parametrize("tile0,ntile", [(1, 703), (37, 200), (63, 2)])
 def test_crafted_ranges(gpu, oracle, tile0, ntile):
-    want, data, dims = crafted(oracle)
+    want, data, dims = _crafted(oracle)
     got, res = gpu_decode(data, len(data), dims, tile0, ntile)
     assert res == [len(data), U64, 0]
     assert np.array_equal(got, want[tile0:tile0 + ntile])
@@ -96,7 +52,7 @@ def test_crafted_ranges(gpu, oracle, tile0, ntile):
 
 @pytest.mark.parametrize("nt", [1, 63, 64, 65, 4097])
 def test_tile_counts(gpu, nt):
-    coef, data, dims = encoded(nt)
+    coef, data, dims = _encoded(nt)
     ranges = [(0, nt), (0, 1), (nt - 1, 1)]
     if nt == 4097:
         ranges += [(4095, 2), (64, 64)]
@@ -111,7 +67,7 @@ def test_tile_counts(gpu, nt):
 def test_three_images(gpu):
     import torch
     from lz4jpeg import jpeg
-    coef, data, dims = encoded(45, 40, 24, 3)
+    coef, data, dims = _encoded(45, 40, 24, 3)
     got, res = gpu_decode(data, len(data), dims, 15, 15)
     assert res == [len(data), U64, 0]
     assert np.array_equal(got, coef[15:30])
@@ -141,7 +97,7 @@ def test_bytes_past_the_stream_do_not_matter(gpu, oracle, tile0, ntile):
     """in_len exact, 64 bytes of 0x00 or of 0xFF behind it (the crafted batch's
     last groups hold full slots and streams that end on a byte's last bit), and
     the stream at 0, 3 and 13 bytes off a 16-B boundary."""
-    want, data, dims = crafted(oracle)
+    want, data, dims = _crafted(oracle)
     runs = [gpu_decode(data, len(data), dims, tile0, ntile, tail=bytes([fill]) * 64, lead=lead)
             for fill, lead in ((0x00, 0), (0xFF, 0), (0x00, 3), (0xFF, 13))]
     for got, res in runs:
@@ -152,40 +108,10 @@ def test_bytes_past_the_stream_do_not_matter(gpu, oracle, tile0, ntile):
 
 # ---- header, index and record errors ---------------------------------------------
 
-def _mutations(good):
-    """test_gpu_jpeg_pack._mutations, restated: (name, bytes, in_len, verdict,
-    malformed tile or None) of one good 65-tile stream."""
-    nt = 65
-    sizes = np.frombuffer(good[16:16 + 2 * nt], "<u2").astype(np.int64)
-    offs = 16 + 2 * nt + np.concatenate([[0], np.cumsum(sizes)])
-
-    def put(pos, raw):
-        b = bytearray(good)
-        b[pos:pos + len(raw)] = raw
-        return bytes(b)
-
-    def stream_at(t, c):
-        p = int(offs[t])
-        for _ in range(c):
-            ncodes, nbits = good[p + 1], int.from_bytes(good[p + 2:p + 4], "little")
-            p += 4 + 3 * ncodes + (nbits + 7) // 8
-        return p
-
-    i40 = 16 + 2 * 40
-    return [("in_len - 1", good, len(good) - 1, 0, None),
-            ("magic", put(0, b"K"), len(good), 0, None),
-            ("h in the header", put(8, (16).to_bytes(4, "little")), len(good), 0, None),
-            ("index entry 40 + 1", put(i40, (int(sizes[40]) + 1).to_bytes(2, "little")),
-             len(good), 0, None),
-            ("tile 40 luma ncodes = 129", put(stream_at(40, 0) + 1, bytes([129])), len(good), 41, 40),
-            ("tile 64 Cb nbits = 513", put(stream_at(64, 2) + 2, (513).to_bytes(2, "little")),
-             len(good), 65, 64)]
-
-
 @pytest.mark.parametrize("k", range(6))
 def test_malformed_streams(gpu, k):
-    coef, good, dims = encoded(65)
-    name, data, in_len, verdict, bad = _mutations(good)[k]
+    coef, good, dims = _encoded(65)
+    name, data, in_len, verdict, bad = jpr_mutations(good)[k]
     implied, want_verdict = J.unpack(data[:in_len], dims)[3:]
     assert want_verdict == verdict, name
     got, res = gpu_decode(data, in_len, dims)
@@ -199,8 +125,8 @@ def test_malformed_streams(gpu, k):
 
 
 def test_malformed_record_outside_the_range(gpu):
-    coef, good, dims = encoded(65)
-    name, data, in_len, verdict, bad = _mutations(good)[4]
+    coef, good, dims = _encoded(65)
+    name, data, in_len, verdict, bad = jpr_mutations(good)[4]
     assert (verdict, bad) == (41, 40)
     got, res = gpu_decode(data, in_len, dims, 41, 24)
     assert res == [len(data), U64, 0]
@@ -286,7 +212,7 @@ def test_graph_capture(gpu):
     replay's count, not a running one."""
     import torch
     from lz4jpeg import jpeg
-    coef, good, dims = encoded(65)
+    coef, good, dims = _encoded(65)
     offs = _stream_offsets(good, 65)
     pick = next((t, 0) for t in range(65) if good[int(offs[t, 0]) + 1] > 1)
     bad = _bump_rle_len(good, offs, [pick])
@@ -294,8 +220,7 @@ def test_graph_capture(gpu):
     d_in = torch.zeros(n, dtype=torch.uint8, device="cuda")
     d_coef = torch.zeros(65 * 128, dtype=torch.int16, device="cuda")
     d_res = torch.full((3,), 7, dtype=torch.int64, device="cuda")
-    scratch = torch.empty(int(jpeg._lib.lib().jpegr_pack_scratch_bytes(65)), dtype=torch.uint8,
-                          device="cuda")
+    scratch = pack_scratch(65)
 
     def call():
         jpeg.decode_stream_device(d_in, n, *dims, d_coef=d_coef, d_result=d_res, scratch=scratch)

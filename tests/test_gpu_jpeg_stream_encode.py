@@ -18,18 +18,13 @@ import pytest
 import entropy_inputs as E
 import jpr_format as J
 import jpt_format as T
-import jpt_inputs as I
 import oracle_api
+from jpr_gpu_lib import U64, coef_dev, image, random_coef, vp
 
 pytestmark = pytest.mark.gpu
 
-U64 = (1 << 64) - 1
 FILL, GUARD, ROOM = 0xEE, 4096, 4096
 FORMATS = [False, True]                                 # tight: JPR1, JPT1
-
-
-def _vp(t, off=0):
-    return ctypes.c_void_p(t.data_ptr() + off)
 
 
 def _dims(nt):
@@ -69,8 +64,7 @@ def _want(arrays, dims, tight):
 def image_case(oracle, w, h, nimg, kind):
     """(coefficients [nt, 128] by the oracle's encoder, slot arrays of the
     oracle's entropy records) of nimg images."""
-    imgs = [oracle.rand_image(w, h, seed=1 + i) if kind == "rand" else I.smooth_image(w, h)
-            for i in range(nimg)]
+    imgs = [image(oracle, w, h, kind, seed=1 + i) for i in range(nimg)]
     coef = np.concatenate([oracle.jpeg_encode(im) for im in imgs]).reshape(-1, 128)
     return coef, slots_of(_records(oracle, coef))
 
@@ -82,8 +76,8 @@ def batch_case(oracle, name):
 
 @functools.lru_cache(maxsize=None)
 def encoded65(oracle):
-    """test_gpu_jpeg_tight.encoded65's coefficients."""
-    coef = np.random.default_rng(1065).integers(-3, 4, size=(65, 128)).astype(np.int16)
+    """jpr_gpu_lib.encoded(65)'s coefficients."""
+    coef = random_coef(65)
     return coef, slots_of(_records(oracle, coef))
 
 
@@ -110,8 +104,8 @@ class Run:
         import torch
         s = stream if stream is not None else torch.cuda.current_stream()
         rc = self.L.jpegr_stream_encode_device(
-            _vp(d_coef), *self.dims, 2 if self.tight else 1, _vp(self.out), self.cap, _vp(self.len),
-            _vp(self.scr, GUARD), _vp(self.res), ctypes.c_void_p(s.cuda_stream))
+            vp(d_coef), *self.dims, 2 if self.tight else 1, vp(self.out), self.cap, vp(self.len),
+            vp(self.scr, GUARD), vp(self.res), ctypes.c_void_p(s.cuda_stream))
         assert rc == 0
 
     def result(self):
@@ -125,15 +119,10 @@ class Run:
                 [int(x) & U64 for x in self.res.cpu().tolist()])
 
 
-def _coef_dev(coef):
-    import torch
-    return torch.from_numpy(np.array(coef, np.int16).reshape(-1)).cuda()
-
-
 def gpu_encode(coef, dims, tight, cap=None):
     import torch
     run = Run(coef.shape[0], dims, tight, cap)
-    run(_coef_dev(coef))
+    run(coef_dev(coef))
     torch.cuda.synchronize()
     return run.result()
 
@@ -143,7 +132,7 @@ def two_stage(coef, dims, tight):
     import torch
     from lz4jpeg import jpeg
     ent = jpeg.Entropy(coef.shape[0])
-    ent.encode(_coef_dev(coef))
+    ent.encode(coef_dev(coef))
     d_out, d_len = jpeg.pack_device(ent, *dims, tight=tight)
     torch.cuda.synchronize()
     assert int(ent.status[0].item()) == 0
@@ -263,7 +252,7 @@ def test_graph_capture(gpu, oracle, tight):
     lengths = []
     for coef, arrays in ((coef_a, arrays_a), (coef_b, arrays_b), (coef_a, arrays_a)):
         want = _want(arrays, dims, tight)
-        d_coef.copy_(_coef_dev(coef))
+        d_coef.copy_(coef_dev(coef))
         run.out.fill_(FILL)
         g.replay()
         torch.cuda.synchronize()
@@ -280,7 +269,7 @@ def test_two_calls_in_flight(gpu, oracle, tight):
     cases = [image_case(oracle, 520, 512, 1, "rand"), image_case(oracle, 520, 512, 1, "smooth")]
     dims = (520, 512, 1)
     runs = [Run(4160, dims, tight), Run(4160, dims, tight)]
-    d_coefs = [_coef_dev(c[0]) for c in cases]
+    d_coefs = [coef_dev(c[0]) for c in cases]
     streams = [torch.cuda.Stream(), torch.cuda.Stream()]
     torch.cuda.synchronize()
     for _ in range(3):
@@ -302,7 +291,7 @@ def test_round_trip(gpu, oracle, tight):
     for coef, dims in ((image_case(oracle, 72, 40, 3, "rand")[0], (72, 40, 3)),
                        (batch_case(oracle, "values")[0], _dims(E.encoder_batch("values").coef.shape[0]))):
         assert coef.shape[0] == J.ntiles_of(*dims)
-        d_coef = _coef_dev(coef)
+        d_coef = coef_dev(coef)
         d_out, d_len, d_res = jpeg.encode_stream_device(d_coef, *dims, tight=tight)
         n = int(d_len.item())
         assert d_res.cpu().tolist() == [n, 0]
@@ -333,5 +322,5 @@ def test_exact_encode_grows(gpu, oracle, tight):
     coef, arrays = batch_case(oracle, "size65_defer")
     want = _want(arrays, _dims(65), tight)
     for cap in (16, len(want) // 2, len(want), None):
-        d_out, over = jpeg.encode_stream_exact_device(_coef_dev(coef), *_dims(65), tight=tight, cap=cap)
+        d_out, over = jpeg.encode_stream_exact_device(coef_dev(coef), *_dims(65), tight=tight, cap=cap)
         assert over == 0 and d_out.cpu().numpy().tobytes() == want, cap

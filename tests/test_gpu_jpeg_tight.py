@@ -9,7 +9,6 @@ the same slots -- never the JPT1 path's own output.
 Tile counts: both pack kernels take a run of 16 tiles per workgroup, the scan
 groups 64 tiles and its partials 4,096; 1, 15, 136 and 4,160 tiles sit in a
 lone wave, a part-filled workgroup, past a scan group and past a partial."""
-import ctypes
 import functools
 import os
 import subprocess
@@ -21,33 +20,13 @@ import entropy_inputs as E
 import jpr_format as J
 import jpt_format as T
 import jpt_inputs as I
+from jpr_gpu_lib import (SENTINEL, U64, crafted, current_stream, encode_slots, encoded, gpu_decode, image,
+                         pack_scratch, slot_arrays, to_dev, vp)
 
 pytestmark = pytest.mark.gpu
 
-U64 = (1 << 64) - 1
-SENTINEL = 12345
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(REPO, "lz4-jpeg_amd", "bin")
-
-
-def _vp(t, off=0):
-    return ctypes.c_void_p(t.data_ptr() + off)
-
-
-def _stream():
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _dev(a, dtype):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype).reshape(-1).view(np.uint8).copy()).cuda()
-
-
-def _scratch(nt):
-    import torch
-    from lz4jpeg import _lib
-    return torch.empty(int(_lib.lib().jpegr_pack_scratch_bytes(nt)), dtype=torch.uint8, device="cuda")
 
 
 def gpu_pack_tight(arrays, w, h, nimg, cap=None, room=0, sentinel=0xEE):
@@ -56,37 +35,16 @@ def gpu_pack_tight(arrays, w, h, nimg, cap=None, room=0, sentinel=0xEE):
     import torch
     from lz4jpeg import _lib
     L = _lib.lib()
-    bits, meta, table = _dev(arrays[0], np.uint8), _dev(arrays[1], np.uint32), _dev(arrays[2], np.uint32)
+    bits, meta, table = (to_dev(a, t) for a, t in zip(arrays, (np.uint8, np.uint32, np.uint32)))
     bound = int(L.jpegr_pack_bound(w, h, nimg))
     out = torch.full((bound + room,), sentinel, dtype=torch.uint8, device="cuda")
     d_len = torch.zeros(1, dtype=torch.int64, device="cuda")
-    scr = _scratch(J.ntiles_of(w, h, nimg))
-    rc = L.jpegr_pack_tight_device(_vp(bits), _vp(meta), _vp(table), w, h, nimg, _vp(out),
-                                   bound if cap is None else cap, _vp(d_len), _vp(scr), _stream())
+    scr = pack_scratch(J.ntiles_of(w, h, nimg))
+    rc = L.jpegr_pack_tight_device(vp(bits), vp(meta), vp(table), w, h, nimg, vp(out),
+                                   bound if cap is None else cap, vp(d_len), vp(scr), current_stream())
     assert rc == 0
     torch.cuda.synchronize()
     return out.cpu().numpy().tobytes(), int(d_len.item())
-
-
-def gpu_decode(data, in_len, dims, tile0=0, ntile=None, tail=b"", lead=0):
-    """test_gpu_jpeg_stream.gpu_decode: (coefficients [ntile, 128], [implied,
-    verdict, rejected] as unsigned) of the direct decode of data[:in_len],
-    `lead` bytes into its buffer, data[in_len:] + tail behind it."""
-    import torch
-    from lz4jpeg import jpeg
-    w, h, nimg = dims
-    nt = J.ntiles_of(w, h, nimg)
-    ntile = nt - tile0 if ntile is None else ntile
-    buf = torch.from_numpy(np.frombuffer(bytes(lead) + bytes(data) + bytes(tail), np.uint8).copy()).cuda()
-    big = torch.full((ntile * 128 + 128,), SENTINEL, dtype=torch.int16, device="cuda")
-    view = big[64:64 + ntile * 128]
-    assert view.data_ptr() % 16 == 0
-    res = torch.full((3,), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64, device="cuda")
-    jpeg.decode_stream_device(buf[lead:], in_len, w, h, nimg, tile0, ntile, d_coef=view, d_result=res)
-    torch.cuda.synchronize()
-    host = big.cpu().numpy()
-    assert (host[:64] == SENTINEL).all() and (host[-64:] == SENTINEL).all()
-    return host[64:-64].reshape(ntile, 128).copy(), [int(x) & U64 for x in res.cpu().tolist()]
 
 
 def slot_decode(arrays):
@@ -95,34 +53,13 @@ def slot_decode(arrays):
     from lz4jpeg import jpeg
     nt = arrays[1].shape[0]
     ent = jpeg.Entropy(nt)
-    ent.bits.copy_(_dev(arrays[0], np.uint8))
-    ent.meta.copy_(_dev(arrays[1], np.uint32).view(torch.int32))
-    ent.table.copy_(_dev(arrays[2], np.uint32).view(torch.int32))
+    ent.bits.copy_(to_dev(arrays[0], np.uint8))
+    ent.meta.copy_(to_dev(arrays[1], np.uint32).view(torch.int32))
+    ent.table.copy_(to_dev(arrays[2], np.uint32).view(torch.int32))
     out = torch.full((nt * 128,), SENTINEL, dtype=torch.int16, device="cuda")
     ent.decode(out)
     torch.cuda.synchronize()
     return out.cpu().numpy().reshape(nt, 128), int(ent.status[1].item())
-
-
-def _host(ent, nt):
-    return (ent.bits.cpu().numpy().reshape(nt, 256), ent.meta.cpu().numpy().view(np.uint32).reshape(nt, 3),
-            ent.table.cpu().numpy().view(np.uint32).reshape(nt, 256))
-
-
-def encode_slots(coef):
-    """The GPU entropy encoder's slots of coefficients [nt, 128], on the host."""
-    import torch
-    from lz4jpeg import jpeg
-    nt = coef.shape[0]
-    ent = jpeg.Entropy(nt)
-    ent.encode(torch.from_numpy(np.array(coef, np.int16).reshape(-1)).cuda())
-    torch.cuda.synchronize()
-    assert int(ent.status[0].item()) == 0
-    return _host(ent, nt)
-
-
-def _image(oracle, w, h, kind, seed=1):
-    return oracle.rand_image(w, h, seed=seed) if kind == "rand" else I.smooth_image(w, h)
 
 
 @functools.lru_cache(maxsize=None)
@@ -130,27 +67,18 @@ def image_slots(oracle, w, h, kind, nimg=1):
     """(slot arrays, coefficients) of nimg images through encode_device and Entropy.encode."""
     import torch
     from lz4jpeg import jpeg
-    img = np.concatenate([_image(oracle, w, h, kind, seed=1 + i).reshape(-1) for i in range(nimg)])
+    img = np.concatenate([image(oracle, w, h, kind, seed=1 + i).reshape(-1) for i in range(nimg)])
     d_coef = jpeg.encode_device(torch.from_numpy(img).cuda(), w, h, nimg)
     coef = d_coef.cpu().numpy().reshape(-1, 128)
     return encode_slots(coef), coef
 
 
 @functools.lru_cache(maxsize=None)
-def crafted(oracle):
-    cb = E.crafted_batch(oracle)
-    bits, meta, table, want = E.pack(cb.streams)
-    nt = len(cb.streams)
-    return (bits, meta, table), want, (8 * nt, 8, 1)
-
-
-@functools.lru_cache(maxsize=None)
 def encoded65():
-    """65 tiles of rng.integers(-3, 4) (test_gpu_jpeg_stream.encoded): slots,
-    coefficients, the restatement's JPT1 stream, dims."""
-    coef = np.random.default_rng(1065).integers(-3, 4, size=(65, 128)).astype(np.int16)
-    arrays = encode_slots(coef)
-    return arrays, coef, T.pack(*arrays, 520, 8, 1), (520, 8, 1)
+    """jpr_gpu_lib.encoded(65): slots, coefficients, the restatement's JPT1
+    stream, dims."""
+    arrays, coef, dims = encoded(65)
+    return arrays, coef, T.pack(*arrays, *dims), dims
 
 
 def _check_pack(arrays, dims, name=""):
@@ -389,7 +317,7 @@ def test_graph_capture(gpu):
     d_len = torch.zeros(1, dtype=torch.int64, device="cuda")
     d_res = torch.full((3,), 7, dtype=torch.int64, device="cuda")
     d_back = torch.zeros(nt * 128, dtype=torch.int16, device="cuda")
-    s1, s2 = _scratch(nt), _scratch(nt)
+    s1, s2 = pack_scratch(nt), pack_scratch(nt)
 
     def both():
         jpeg.pack_device(ent, w, h, nimg, d_out=d_out, d_len=d_len, scratch=s1, tight=True)
@@ -411,7 +339,7 @@ def test_graph_capture(gpu):
         d_coef = torch.from_numpy(coef.reshape(-1)).cuda()
         ent.encode(d_coef)
         torch.cuda.synchronize()
-        want = T.pack(*_host(ent, nt), w, h, nimg)
+        want = T.pack(*slot_arrays(ent, nt), w, h, nimg)
         assert len(want) == len(want_a)
         d_out.zero_()
         d_back.fill_(SENTINEL)
@@ -429,7 +357,7 @@ def test_graph_capture(gpu):
 def test_compress_decompress(gpu, oracle, w, h, nimg, kind):
     import torch
     from lz4jpeg import jpeg
-    img = np.concatenate([_image(oracle, w, h, kind, seed=1 + i).reshape(-1) for i in range(nimg)])
+    img = np.concatenate([image(oracle, w, h, kind, seed=1 + i).reshape(-1) for i in range(nimg)])
     d_img = torch.from_numpy(img).cuda()
     tight = jpeg.compress_device(d_img, w, h, nimg, tight=True)
     plain = jpeg.compress_device(d_img, w, h, nimg)

@@ -10,14 +10,11 @@ the last run is a single tile.  The caps sit around the header and the index
 (I = 16 + 2 * 33), and 17, 16, 15, 1 and 0 B either side of each run's first
 byte and of the stream's end, so a clipped flush ends before, on and after a
 chunk boundary, in a whole chunk and in either shared one."""
-import ctypes
-
 import numpy as np
 import pytest
 
-import jpr_format as J
 import jpt_format as T
-import test_gpu_jpeg_pack as P
+from jpr_gpu_lib import Slots, coef_dev, current_stream, encoded, encoded_jpr, pack_scratch, vp
 
 pytestmark = pytest.mark.gpu
 
@@ -25,10 +22,6 @@ NT, DIMS = 33, (264, 8, 1)
 ROOM, FILL = 4096, 0xEE
 INDEX_END = 16 + 2 * NT
 WRITERS = ["pack", "pack_tight", "stream_encode", "stream_encode_tight"]
-
-
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 def _caps(want):
@@ -51,12 +44,12 @@ class Writer:
         self.L = _lib.lib()
         self.name, self.tight = name, name.endswith("tight")
         self.bound = int(self.L.jpegr_pack_bound(*DIMS))
-        self.st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        self.st = current_stream()
         if name.startswith("pack"):
-            self.slots = P.Slots(NT).load(*arrays)
-            self.scr = torch.empty(int(self.L.jpegr_pack_scratch_bytes(NT)), dtype=torch.uint8, device="cuda")
+            self.slots = Slots(NT).load(*arrays)
+            self.scr = pack_scratch(NT)
         else:
-            self.coef = torch.from_numpy(coef.reshape(-1).copy()).cuda()
+            self.coef = coef_dev(coef)
 
     def __call__(self, cap):
         import torch
@@ -65,14 +58,14 @@ class Writer:
         if self.name.startswith("pack"):
             fn = self.L.jpegr_pack_tight_device if self.tight else self.L.jpegr_pack_device
             s = self.slots
-            rc = fn(_vp(s.bits), _vp(s.meta), _vp(s.table), *DIMS, _vp(out), cap, _vp(d_len),
-                    _vp(self.scr), self.st)
+            rc = fn(vp(s.bits), vp(s.meta), vp(s.table), *DIMS, vp(out), cap, vp(d_len),
+                    vp(self.scr), self.st)
         else:
             scr = torch.empty(int(self.L.jpegr_stream_encode_scratch_bytes(NT, cap)), dtype=torch.uint8,
                               device="cuda")
             res = torch.zeros(2, dtype=torch.int64, device="cuda")
-            rc = self.L.jpegr_stream_encode_device(_vp(self.coef), *DIMS, 2 if self.tight else 1, _vp(out),
-                                                   cap, _vp(d_len), _vp(scr), _vp(res), self.st)
+            rc = self.L.jpegr_stream_encode_device(vp(self.coef), *DIMS, 2 if self.tight else 1, vp(out),
+                                                   cap, vp(d_len), vp(scr), vp(res), self.st)
         assert rc == 0
         torch.cuda.synchronize()
         return out.cpu().numpy().tobytes(), int(d_len.item())
@@ -80,9 +73,9 @@ class Writer:
 
 @pytest.mark.parametrize("name", WRITERS)
 def test_caps(gpu, name):
-    arrays, coef, want_r, dims = P.encoded(NT, *DIMS)
+    arrays, coef, dims = encoded(NT, *DIMS)
     assert dims == DIMS
-    want = T.pack(*arrays, *DIMS) if name.endswith("tight") else want_r
+    want = T.pack(*arrays, *DIMS) if name.endswith("tight") else encoded_jpr(NT, *DIMS)
     caps = _caps(want)
     assert len(caps) >= 30 and caps[-1] == len(want) + 17
     writer = Writer(name, arrays, coef)

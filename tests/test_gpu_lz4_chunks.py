@@ -21,9 +21,8 @@ import pytest
 
 import golden_inputs
 import lz4_chunk_lib
-from test_gpu_lz4_runs import _block_types
+from lz4_seq_inputs import BLK, Expected, block_types
 
-BLK = 300
 C = 1 << lz4_chunk_lib.CHUNK12_LOG2            # blocks per chunk of the variant
 THREE = (2 * C + 33, 277)                      # three chunks: the middle one is neither first nor last
 # (blocks, bytes of the last block)
@@ -40,29 +39,21 @@ class Content:
         self.data, self.blocks = data, blocks
 
 
-class Case:
+class Case(Expected):
     """A prefix of a content: nb blocks, the last of last_n bytes."""
 
     def __init__(self, oracle, content, nb, last_n):
-        self.nb, self.n = nb, BLK * (nb - 1) + last_n
-        self.data = content.data[:self.n]
-        last = content.blocks[nb - 1] if last_n == BLK else oracle.lz4_blocks(
-            np.frombuffer(self.data[BLK * (nb - 1):], np.uint8), 0, 1)
-        self.blocks = content.blocks[:nb - 1] + [last]
-        self.sizes = np.array([len(b) for b in self.blocks], np.uint64)
-        self.offsets = np.concatenate(([0], np.cumsum(self.sizes)[:-1])).astype(np.uint64)
-        self.body = b"".join(self.blocks)
-
-    def want(self, hdr):
-        return bytes([self.nb & 0xFF]) + self.body if hdr else self.body
+        super().__init__(oracle, content.data[:BLK * (nb - 1) + last_n], known=content.blocks)
+        assert self.nb == nb
+        self.n = len(self.data)
 
 
 @pytest.fixture(scope="module")
 def types(oracle):
-    """The five block types of test_gpu_lz4_runs and their encodings; what
+    """The five block types of lz4_seq_inputs and their encodings; what
     each type is for is asserted from the oracle's result."""
     text = golden_inputs.lz4_input("metamorphosis_spaces")
-    t = _block_types(text)
+    t = block_types(text)
     enc = [oracle.lz4_blocks(np.frombuffer(x, np.uint8), 0, 1) for x in t]
     m = [oracle.lz4_matches(x) for x in t]
     # block header: u8 sequence count, u16 size (LZ4.c:415-425)
@@ -121,8 +112,8 @@ def test_constructed_inputs_have_their_properties(oracle, contents):
     their placement at the chunk boundaries.  Here: a case's expectation is
     the oracle's own stream of the same bytes."""
     case = Case(oracle, contents[3], C + 1, 23)
-    assert case.want(1) == oracle.lz4_compress(case.data)
-    assert case.offsets[C] == len(case.body) - len(case.blocks[C])
+    assert case.framed() == oracle.lz4_compress(case.data)
+    assert case.offsets()[C] == len(case.body()) - len(case.blocks[C])
     assert SIZES[-1] == THREE and -(-THREE[0] // C) == 3
 
 
@@ -177,27 +168,28 @@ def _verify(ctx, case, mode, buf, word, start, cap=None):
     """Everything the call left behind, against the oracle; a mismatch names
     the first differing block and the chunk it lies in."""
     hdr = 1 if mode == "framed" else 0
-    want = np.frombuffer(case.want(hdr), np.uint8)
+    want = np.frombuffer(case.framed() if hdr else case.body(), np.uint8)
     per = lz4_chunk_lib.chunk_blocks(ctx.name)
     what = f"{ctx.name}, {case.nb} blocks ({-(-case.nb // per)} chunks), {mode}"
 
     def where(b):
         return f"{what}: block {b} (block {b % per} of chunk {b // per})"
     assert word >> 63 == 0, f"{what}: bit 63 of the length word (a corrupt bucket head)"
-    offs, sizes = ctx.block_offsets(case.nb), ctx.block_sizes(case.nb)
-    bad = np.flatnonzero(sizes != case.sizes)
+    offs, sizes = ctx.block_offsets(case.nb).astype(np.int64), ctx.block_sizes(case.nb)
+    want_offs, want_sizes = case.offsets(), case.sizes()
+    bad = np.flatnonzero(sizes != want_sizes)
     assert not bad.size, f"{where(int(bad[0]) if bad.size else 0)}: size {sizes[bad[:1]]}, want " \
-                         f"{case.sizes[bad[:1]]}"
-    bad = np.flatnonzero(offs != case.offsets)
+                         f"{want_sizes[bad[:1]]}"
+    bad = np.flatnonzero(offs != want_offs)
     assert not bad.size, f"{where(int(bad[0]) if bad.size else 0)}: offset {offs[bad[:1]]}, want " \
-                         f"{case.offsets[bad[:1]]}"
+                         f"{want_offs[bad[:1]]}"
     assert word == want.size, f"{what}: length word {word}, want {want.size}"
     written = min(want.size, want.size if cap is None else cap)
     got = buf[start:start + written]
     bad = np.flatnonzero(got != want[:written])
     if bad.size:
         i = int(bad[0])
-        b = int(np.searchsorted(case.offsets + hdr, i, side="right")) - 1
+        b = int(np.searchsorted(want_offs + hdr, i, side="right")) - 1
         raise AssertionError(f"{where(max(b, 0))}: stream byte {i} is {got[i]:#x}, want "
                              f"{want[i]:#x} ({bad.size} bytes differ)")
     assert (buf[:start] == 0xEE).all(), f"{what}: bytes before the output were written"
@@ -252,12 +244,12 @@ def test_unaligned_output(ctx, three, out_off):
 
 
 def _caps(case):
-    at_c = 1 + int(case.offsets[C])              # stream offset of block C (framed)
-    full = 1 + len(case.body)
-    caps = [at_c - 1, at_c, at_c + 1, 1 + int(case.offsets[C + C // 2]) + 7,
-            1 + int(case.offsets[2 * C + 10]) + 5, full - 1, full]
-    assert caps == sorted(caps) and 1 + int(case.offsets[2 * C]) < caps[4] < full - 1
-    assert caps[2] < caps[3] < 1 + int(case.offsets[2 * C])
+    offs = 1 + case.offsets()                    # stream offsets of the blocks (framed)
+    at_c, full = int(offs[C]), len(case.framed())
+    caps = [at_c - 1, at_c, at_c + 1, int(offs[C + C // 2]) + 7, int(offs[2 * C + 10]) + 5,
+            full - 1, full]
+    assert caps == sorted(caps) and int(offs[2 * C]) < caps[4] < full - 1
+    assert caps[2] < caps[3] < int(offs[2 * C])
     return caps
 
 
@@ -266,7 +258,7 @@ def _caps(case):
 def test_capacity(ctx, three, k):
     import torch
     cap = _caps(three)[k]
-    full = 1 + len(three.body)
+    full = len(three.framed())
     # async: every byte below cap, nothing at or past it, the full length
     buf, word, start = _run(ctx, three, "framed", cap=cap)
     _verify(ctx, three, "framed", buf, word, start, cap)

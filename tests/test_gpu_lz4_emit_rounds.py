@@ -3,9 +3,9 @@ rounds of 64 flattened records (csrc/lz4r_emit.h, emit_records).
 
 Every case compares, against the oracle's per-block encodings of the same
 bytes, the whole stream byte for byte, the length word (bit 63 clear) and the
-device block offsets.  What a case covers is asserted from the oracle's own
-encoding (byte 0 of a block = its sequence count), never from the code under
-test.
+device block offsets and sizes (lz4_gpu_lib.check).  What a case covers is
+asserted from the oracle's own encoding (byte 0 of a block = its sequence
+count), never from the code under test.
 
 An emit workgroup is the 32 blocks [32 w, 32 w + 32) of a launch and a scan
 group is 64 blocks, so a case is an input of 1 .. ~100 blocks: a list of
@@ -29,108 +29,21 @@ import numpy as np
 import pytest
 
 import golden_inputs
+import lz4_gpu_lib
+from lz4_gpu_lib import check
+from lz4_seq_inputs import BLK, Expected, block_endmatch, blocks_by_count, enc_of, nseq, planned_input
 
 pytestmark = pytest.mark.gpu
 
-BLK = 300
 WG = 32                                # blocks per lz4_emit workgroup
 ROUND = 64                             # records per round
-
-
-# ---- blocks with a given number of sequences ---------------------------------
-
-def block_exact(k, seed=0):
-    """A block of exactly k sequences, k = 1 .. 53: 40 distinct bytes, then
-    k - 1 copies of 4-grams of them, each followed by a byte value used nowhere
-    else (every match is exactly 4 long), then unused values as the tail."""
-    assert 1 <= k <= 53
-    rng = np.random.default_rng(1000 + 64 * seed + k)
-    vals = [int(v) for v in rng.permutation(256)]
-    pre, unused = vals[:40], vals[40:]
-    out = list(pre)
-    for i in range(k - 1):
-        s = (5 * i) % 37
-        out += pre[s:s + 4] + [unused.pop()]
-    pad = BLK - len(out)
-    u = len(unused)
-    assert pad <= u + u // 2
-    # second pass at stride 2: no pair of the first pass comes back
-    out += unused[:pad] + [unused[(2 * i + 1) % u] for i in range(max(0, pad - u))]
-    assert len(out) == BLK
-    return bytes(out)
-
-
-def _block_dense(seed):
-    rng = np.random.default_rng(seed)
-    p = int(rng.integers(36, 64))
-    pre = [int(v) for v in rng.permutation(256)[:p]]
-    out = list(pre)
-    while len(out) < BLK:
-        s = int(rng.integers(0, p - 3))
-        out += pre[s:s + 4]
-    return bytes(out[:BLK])
-
-
-def block_packed(p, seed=0):
-    """p distinct bytes, then 4-grams of them back to back with no pair of
-    neighbours used twice and none continuing its predecessor: (300 - p) / 4
-    matches of exactly 4."""
-    assert (BLK - p) % 4 == 0 and p >= 12
-    rng = np.random.default_rng(7000 + seed)
-    pre = [int(v) for v in rng.permutation(256)[:p]]
-    out, seen, last = list(pre), set(), None
-    while len(out) < BLK:
-        s = int(rng.integers(0, p - 3))
-        if last is not None and (s == last + 4 or (last, s) in seen or s == last):
-            continue
-        seen.add((last, s))
-        out += pre[s:s + 4]
-        last = s
-    return bytes(out)
-
-
-def block_endmatch(k, seed=0):
-    """block_exact's form with the tail cut short by a last 4-gram copy: the
-    block's last record is a match that ends with the block."""
-    rng = np.random.default_rng(3000 + 64 * seed + k)
-    vals = [int(v) for v in rng.permutation(256)]
-    pre, unused = vals[:40], vals[40:]
-    out = list(pre)
-    for i in range(k - 2):
-        s = (5 * i) % 37
-        out += pre[s:s + 4] + [unused.pop()]
-    pad = BLK - 4 - len(out)
-    assert 0 <= pad <= len(unused)
-    out += unused[:pad] + pre[33:37]
-    assert len(out) == BLK
-    return bytes(out)
-
-
-def enc_of(oracle, blk):
-    return oracle.lz4_blocks(np.frombuffer(blk, dtype=np.uint8), 0, 1)
-
-
-def nseq(oracle, blk):
-    return enc_of(oracle, blk)[0]
 
 
 @pytest.fixture(scope="module")
 def blocks(oracle):
     """{sequence count: block} for 1 .. 65 and whatever the packed blocks
     reach above, each count asserted on the oracle."""
-    by = {}
-    for k in range(1, 54):
-        by[k] = block_exact(k)
-        assert nseq(oracle, by[k]) == k, k
-    for seed in range(400):
-        b = _block_dense(seed)
-        by.setdefault(nseq(oracle, b), b)
-    assert all(k in by for k in range(54, 66)), sorted(k for k in by if k > 53)
-    for p in (36, 32, 28, 24, 20):
-        for seed in range(4):
-            b = block_packed(p, seed)
-            by.setdefault(nseq(oracle, b), b)
-    return by
+    return blocks_by_count(oracle)
 
 
 @pytest.fixture(scope="module")
@@ -140,103 +53,14 @@ def text():
 
 @pytest.fixture(scope="module")
 def comp(gpu):
-    from lz4jpeg.lz4 import Compressor
-    c = Compressor()
-    yield c
-    c.close()
-
-
-class Expected:
-    """The oracle's per-block encodings of one input, computed once."""
-
-    def __init__(self, oracle, data):
-        self.data = bytes(data)
-        buf = np.frombuffer(self.data, dtype=np.uint8)
-        self.nb = (len(self.data) + BLK - 1) // BLK
-        self.blocks = [oracle.lz4_blocks(buf, b, b + 1) for b in range(self.nb)]
-
-    def counts(self):
-        return [b[0] for b in self.blocks]
-
-    def sizes(self):
-        return np.array([len(b) for b in self.blocks], dtype=np.int64)
-
-    def offsets(self):
-        return np.concatenate(([0], np.cumsum(self.sizes())[:-1]))
-
-    def body(self):
-        return b"".join(self.blocks)
-
-    def framed(self):
-        return bytes([self.nb & 0xFF]) + self.body()
-
-
-def _compress(comp, data, misalign=0, lead=0, cap=None, segment=False, final_shard=None):
-    """-> (the whole output buffer, the length word, the device block offsets);
-    the buffer is 0xEE where the call wrote nothing, and the call's capacity
-    is `cap` (default: all of it)."""
-    import torch
-    from lz4jpeg.lz4 import compress_bound
-    n = len(data)
-    d_buf = torch.empty(misalign + n, dtype=torch.uint8, device="cuda")
-    assert d_buf.data_ptr() % 4 == 0
-    d_in = d_buf[misalign:]
-    d_in.copy_(torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()))
-    d_all = torch.full((lead + compress_bound(n) + 64,), 0xEE, dtype=torch.uint8, device="cuda")
-    assert d_all.data_ptr() % 16 == 0
-    d_out = d_all[lead:] if cap is None else d_all[lead:lead + cap]
-    d_len = torch.full((1,), -1, dtype=torch.int64, device="cuda")
-    comp.compress_async(d_in, n, d_out, d_len, segment=segment, final_shard=final_shard)
-    torch.cuda.synchronize()
-    word = int(d_len.item())
-    assert word >= 0, "bit 63 of the length word: a corrupt bucket head"
-    nb = (n + BLK - 1) // BLK
-    return d_all.cpu().numpy().tobytes(), word, comp.block_offsets(nb)
-
-
-def _check(comp, exp, framed=True, where=None, lead=0, cap=None, **kw):
-    want = exp.framed() if framed else exp.body()
-    buf, word, offs = _compress(comp, exp.data, lead=lead, cap=cap, **kw)
-    assert word == len(want), where
-    lim = len(want) if cap is None else min(cap, len(want))
-    got = buf[lead:lead + lim]
-    if got != want[:lim]:
-        # the first block that differs, by the oracle's offsets
-        o = exp.offsets() + (1 if framed else 0)
-        bad = next(b for b in range(exp.nb)
-                   if got[o[b]:o[b] + len(exp.blocks[b])] != exp.blocks[b][:max(0, lim - o[b])])
-        raise AssertionError((where, "block", bad, "of", exp.nb, "counts", exp.counts()[
-            max(0, bad - 4):bad + 2]))
-    assert buf[:lead] == b"\xee" * lead, where
-    assert buf[lead + lim:] == b"\xee" * (len(buf) - lead - lim), where
-    assert np.array_equal(offs.astype(np.int64), exp.offsets()), where
-
-
-def _workgroups(plans, text):
-    """Each plan at the start of a workgroup of its own, padded with text
-    (the last one is not padded: the input ends with it)."""
-    out, pos, full = [], 0, len(text) // BLK
-    for w, plan in enumerate(plans):
-        assert 1 <= len(plan) <= WG
-        out += list(plan)
-        if w + 1 < len(plans):
-            for _ in range(WG - len(plan)):
-                out.append(bytes(text[BLK * pos:BLK * (pos + 1)]))
-                pos = (pos + 1) % full
-    return b"".join(out)
+    yield from lz4_gpu_lib.compressor()
 
 
 def _plan_input(oracle, blocks, text, plans):
     """plans: per workgroup, a list of sequence counts (ints) or ready blocks
-    (bytes).  Every given count is asserted on the oracle's encoding."""
-    wgs = [[blocks[x] if isinstance(x, int) else x for x in plan] for plan in plans]
-    exp = Expected(oracle, _workgroups(wgs, text))
-    got = exp.counts()
-    for w, plan in enumerate(plans):
-        for i, x in enumerate(plan):
-            if isinstance(x, int):
-                assert got[WG * w + i] == x, (w, i, x, got[WG * w + i])
-    return exp
+    (bytes), each at the start of a workgroup of its own, padded with text
+    (the last one is not padded: the input ends with it)."""
+    return planned_input(oracle, blocks, text, plans, WG, pad_last=False)
 
 
 def _starts(exp, w):
@@ -268,7 +92,7 @@ def test_total_at_capacity(comp, oracle, blocks, text, T):
     plans = [_split(T, WG, 2, 40, seed=T), _split(T, WG, 1, 53, seed=T + 1), [12, 9]]
     exp = _plan_input(oracle, blocks, text, plans)
     assert _starts(exp, 0)[1] == T and _starts(exp, 1)[1] == T
-    _check(comp, exp, where=T)
+    check(comp, exp, where=T)
 
 
 def test_total_32_one_sequence_blocks(comp, oracle, blocks, text):
@@ -279,14 +103,14 @@ def test_total_32_one_sequence_blocks(comp, oracle, blocks, text):
         assert enc[0] == 1 and len(enc) > BLK      # one literal run of 300, its extension bytes
     exp = _plan_input(oracle, blocks, text, [rnd, [1] * WG, rnd[:5]])
     assert _starts(exp, 0)[1] == WG and _starts(exp, 1)[1] == WG
-    _check(comp, exp)
+    check(comp, exp)
 
 
 def test_total_above_1024(comp, oracle, blocks, text):
     dense = [54 + (7 * i) % 12 for i in range(WG)]         # 54 .. 65 records each
     exp = _plan_input(oracle, blocks, text, [dense, dense[::-1], dense[:3]])
     assert _starts(exp, 0)[1] > 1024 and _starts(exp, 1)[1] > 1024
-    _check(comp, exp)
+    check(comp, exp)
 
 
 # ---- 2. a flattened index that is a multiple of 64 ---------------------------------
@@ -312,13 +136,13 @@ def test_round_boundary_positions(comp, oracle, blocks, text):
     assert s1[2] - 1 == 64 and s1[4] - 1 == 128
     assert s2[3] - 1 == 64 and exp.counts()[64 + 2] == km
     assert s2[7] - 1 == 192 and exp.counts()[64 + 6] == km
-    _check(comp, exp, where="first / last")
+    check(comp, exp, where="first / last")
     exp = _plan_input(oracle, blocks, text, plans[3:])
     s0, s1 = (_starts(exp, w)[0] for w in range(2))
     assert s0[2] + 1 == 64 and s0[4] + 1 == 128 and exp.counts()[2] == 2 and exp.counts()[4] == 2
     assert all(any(a < m < a + n - 1 for a, n in zip(s1, exp.counts()[32:38]))
                for m in (64, 128, 192, 256))
-    _check(comp, exp, where="single / inside")
+    check(comp, exp, where="single / inside")
 
 
 def test_many_block_starts_in_a_round(comp, oracle, blocks, text):
@@ -332,7 +156,7 @@ def test_many_block_starts_in_a_round(comp, oracle, blocks, text):
         s, T = _starts(exp, w)
         per = [sum(1 for v in s if ROUND * r <= v < ROUND * (r + 1)) for r in range((T + 63) // 64)]
         assert max(per) > 8, per
-    _check(comp, exp)
+    check(comp, exp)
 
 
 # ---- 3. a block of 62 .. 65 records, and one that holds a whole round ------------------
@@ -347,7 +171,7 @@ def test_round_sized_block_positions(comp, oracle, blocks, text, k):
     c = exp.counts()
     assert c[0] == k and c[31] == k and c[32] == k
     assert _starts(exp, 1)[0][3] % ROUND == 63 and _starts(exp, 2)[0][2] == 63
-    _check(comp, exp, where=k)
+    check(comp, exp, where=k)
 
 
 def test_block_across_a_whole_round(comp, oracle, blocks, text):
@@ -362,7 +186,7 @@ def test_block_across_a_whole_round(comp, oracle, blocks, text):
     for w, b in ((0, 2), (2, 3)):
         s = _starts(exp, w)[0][b]
         assert s % ROUND == 63 and s + big > (s // ROUND + 2) * ROUND
-    _check(comp, exp, where=big)
+    check(comp, exp, where=big)
 
 
 # ---- 4. the overflow slot at a round's start ----------------------------------------
@@ -382,7 +206,7 @@ def test_round_starts_inside_overflow(comp, oracle, blocks, text, big):
         s = _starts(exp, w)[0]
         assert exp.counts()[WG * w + 1] == big and exp.counts()[WG * w + 3] == big
         assert -s[1] % ROUND == ja and -s[3] % ROUND == jb   # the round starts at record ja / jb
-    _check(comp, exp, where=big)
+    check(comp, exp, where=big)
 
 
 # ---- 5. edges of the launch ------------------------------------------------------
@@ -392,29 +216,18 @@ def text_blocks(oracle, text):
     return Expected(oracle, text[:BLK * 96]).blocks
 
 
-def _text_case(oracle, text, text_blocks, count, last_n):
-    n = BLK * (count - 1) + last_n
-    exp = Expected.__new__(Expected)
-    exp.data = bytes(text[:n])
-    exp.nb = count
-    last = text_blocks[count - 1] if last_n == BLK else oracle.lz4_blocks(
-        np.frombuffer(exp.data, dtype=np.uint8), count - 1, count)
-    exp.blocks = text_blocks[:count - 1] + [last]
-    return exp
-
-
 @pytest.mark.parametrize("count", (1, 31, 32, 33, 63, 64, 65, 96))
 def test_launch_edges(comp, oracle, text, text_blocks, count):
     for last_n in (1, 23, 24, 300):
-        exp = _text_case(oracle, text, text_blocks, count, last_n)
+        exp = Expected.of_text_prefix(oracle, text, text_blocks, count, last_n)
         if len(exp.data) < BLK:                  # no framed form: a final segment
-            _check(comp, exp, framed=False, where=(count, last_n), segment=True, final_shard=True)
+            check(comp, exp, framed=False, where=(count, last_n), segment=True, final_shard=True)
             continue
-        _check(comp, exp, where=(count, last_n))
-        _check(comp, exp, framed=False, where=(count, last_n, "final"), segment=True,
+        check(comp, exp, where=(count, last_n))
+        check(comp, exp, framed=False, where=(count, last_n, "final"), segment=True,
                final_shard=True)
         if last_n == BLK:                        # a non-final shard is whole blocks
-            _check(comp, exp, framed=False, where=(count, "shard"), segment=True,
+            check(comp, exp, framed=False, where=(count, "shard"), segment=True,
                    final_shard=False)
 
 
@@ -424,12 +237,12 @@ def test_output_and_input_alignment(comp, oracle, blocks, text):
     plans = [[20, 43, 3, 65, 1, 1, b"\x5a" * BLK, 30], [64, 30, 34], [17]]
     exp = _plan_input(oracle, blocks, text, plans)
     for lead in (0, 1, 15):
-        _check(comp, exp, where=("lead", lead), lead=lead)
-        _check(comp, exp, framed=False, where=("lead", lead, "segment"), lead=lead, segment=True,
+        check(comp, exp, where=("lead", lead), lead=lead)
+        check(comp, exp, framed=False, where=("lead", lead, "segment"), lead=lead, segment=True,
                final_shard=True)
     for mis in (1, 2, 3):
-        _check(comp, exp, where=("misalign", mis), misalign=mis)
-    _check(comp, exp, where=("both", 3, 15), misalign=3, lead=15)
+        check(comp, exp, where=("misalign", mis), misalign=mis)
+    check(comp, exp, where=("both", 3, 15), misalign=3, lead=15)
 
 
 # ---- 7. capacity -----------------------------------------------------------------
@@ -451,4 +264,4 @@ def test_capacity(comp, oracle, text, n, length):
         o = 1 + int(exp.offsets()[WG])           # block 32: the second workgroup's first byte
         caps |= {o - 1, o, o + 1}
     for cap in sorted(caps):
-        _check(comp, exp, where=(n, cap), cap=cap)
+        check(comp, exp, where=(n, cap), cap=cap)

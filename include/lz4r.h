@@ -190,6 +190,62 @@ int lz4r_decompress_stream_device(const void *d_in, size_t in_len, void *d_out,
 int lz4r_decompress_stream(const uint8_t *in, size_t in_len, uint8_t *out, size_t cap,
                            size_t *out_len);
 
+/* Random access: many byte ranges of the decoded stream in one call, each
+ * decoded from the 300-byte blocks it covers and from nothing else
+ * (csrc/lz4r_read.hip).  Read r delivers decoded bytes [src, src + len) to
+ * d_out[dst, dst + len).  d_reads: nreads of these on the device. */
+typedef struct lz4r_read { uint64_t src, len, dst; } lz4r_read;
+
+/* Blocks a read of max_len bytes can cover, K = (max_len + 298) / 300 + 1:
+ * the items every read of a call with that max_len occupies.  Host only. */
+size_t lz4r_read_items(size_t max_len);
+
+/* d_in, in_len, d_block_offsets and nb are lz4r_decompress_device's: the
+ * framed stream and the nb uint64 offsets relative to the first block byte
+ * (lz4r_copy_block_offsets, lz4r_block_offsets_device or
+ * lz4r_stream_index_device); block nb - 1 ends at in_len and may be short.
+ * Asynchronous on `stream`; no host read-back and no host state between
+ * calls, so a call can be captured into a graph.  d_result: two uint64 on
+ * the device, reset by the call's own first launch: [0] = the summed len of
+ * the reads that were delivered, [1] = ~0 when every read was delivered, else
+ * 1 + the index of the first bad read.  A read is bad when len > max_len,
+ * when src + len overflows or passes the decoded length (no length argument:
+ * the lane that decodes block nb - 1 knows it), when dst + len > out_cap, or
+ * when a block it covers is malformed (offsets not inside [0, in_len), fewer
+ * than 3 or more than LZ4R_BLOCK_BOUND bytes, or bytes that do not parse).
+ * len == 0 is a good read that writes nothing, whatever its src and dst.
+ * Good reads are delivered exactly whatever the bad ones do; destination
+ * ranges of different reads that overlap hold unspecified bytes.  Whatever
+ * the stream, the offsets and the reads say, nothing outside d_in[0, in_len),
+ * d_block_offsets[0, nb) and d_reads[0, nreads) is read and nothing outside
+ * d_result and each read's own d_out[dst, dst + len) within out_cap is
+ * written: a read that fails on its own fields (len, overflow, capacity, a
+ * block index >= nb) writes nothing, one that fails inside a block may leave
+ * unspecified bytes in its own destination range.
+ * Mapping: every read occupies K = lz4r_read_items(max_len) lanes, one per
+ * block it may cover, so group reads of similar size per call: a batch of
+ * short reads with one long one is correct but idles most lanes.
+ * LZ4R_ERR_ARG, before any HIP call: a NULL pointer; nb, nreads or max_len 0;
+ * in_len < 4; d_reads, d_block_offsets or d_result not 8-byte aligned;
+ * nreads * K items needing more than 2^31 - 1 workgroups of 32.  d_in and
+ * d_out take any alignment. */
+int lz4r_read_device(const void *d_in, size_t in_len, const void *d_block_offsets,
+                     size_t nb, const void *d_reads, size_t nreads, size_t max_len,
+                     void *d_out, size_t out_cap, void *d_result, void *stream);
+
+/* The block offsets of a bare framed stream, kept: the boundary search of
+ * lz4r_decompress_stream_device into the caller's d_block_offsets (cap_blocks
+ * uint64, device), every block then checked by the decoder writing no
+ * output.  Synchronises `stream`.  LZ4R_OK: *nb blocks, *decoded_len decoded
+ * bytes, and d_block_offsets[0, *nb) equal what lz4r_copy_block_offsets gave
+ * the compressing call -- what lz4r_read_device and lz4r_decompress_device
+ * take.  LZ4R_ERR_CAPACITY with *nb = the blocks needed when cap_blocks is
+ * too small (a stream of in_len bytes has at most (in_len - 1) / 8 + 1);
+ * LZ4R_ERR_CORRUPT as lz4r_decompress_stream_device.  A fast pass, then the
+ * exact pass for streams with truncated matches; one host read-back each. */
+int lz4r_stream_index_device(const void *d_in, size_t in_len, void *d_block_offsets,
+                             size_t cap_blocks, size_t *nb, size_t *decoded_len, void *stream);
+
 /* Host convenience wrapper around lz4r_compress_device (copies in and out). */
 int lz4r_compress(const uint8_t *in, size_t n, uint8_t *out, size_t cap,
                   size_t *out_len);

@@ -20,11 +20,6 @@ namespace {
 constexpr int kPfN = 4;                    // L2 lines touched ahead of the walk
 constexpr int kPfS = 128;                  // (2 / 4 / 8 lines, 64 or 128 B apart: same time)
 
-// Slots kSlotS apart: 300 bytes of output and 16 of slack, so a 16-B store
-// that starts inside the block never reaches the next lane's slot (no
-// exact-size stores at the slot end).
-constexpr int kSlotS = kBlk + 16;
-
 struct DecLds {
   alignas(16) uint8_t out[kBPW * kSlotS + 48];  // lane l's block at out[kSlotS l] (+ slack)
   uint4 sel[17];                                 // sel[k]: v_perm selectors, bytes < k from A

@@ -149,6 +149,11 @@ struct Slot {
   }
 };
 
+// Slots kSlotS apart: 300 bytes of output and 16 of slack, so a 16-B store
+// that starts inside the block never reaches the next lane's slot (no
+// exact-size stores at the slot end).
+constexpr int kSlotS = kBlk + 16;
+
 // The output slot of the fast path: every store is a whole 16-B store (the
 // slot's 16-B slack takes what passes its 300 bytes).
 struct SlotW {

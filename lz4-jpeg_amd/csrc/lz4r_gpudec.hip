@@ -24,7 +24,8 @@
 //   lz4r_dec_bare.h    lz4_bare_*: candidates, walk, check / fix, scan,
 //                      offsets and the gate of a bare stream; lz4_decode_init
 //   wave64.h           u32x4
-//   below              the host side: the scratch pool, one bare-stream pass,
+//   below              the host side: the scratch pool, one bare-stream pass
+//                      (a decode, or the index of lz4r_stream_index_device),
 //                      the C ABI
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -91,15 +92,18 @@ hipError_t scratch_alloc(void **ptr, size_t bytes, hipStream_t s) {
 
 // the control words read back after the decode -> the call's return code and
 // *out_len: the gate's verdict first, then a failed block, then the capacity
-int bare_verdict(const unsigned long long *h, size_t out_cap, size_t *out_len) {
+// nb_out (an index call: the blocks are checked and nothing is stored): the
+// block count too, and an output that holds nothing is no error
+int bare_verdict(const unsigned long long *h, size_t out_cap, size_t *out_len, size_t *nb_out) {
   if (h[kCtlGate] == kGateCorrupt) return LZ4R_ERR_CORRUPT;
+  if (nb_out) *nb_out = (size_t)h[kCtlNb];
   if (h[kCtlGate] == kGateCapacity) {                 // at least this much output
     *out_len = (size_t)(h[kCtlNb] - 1) * kBlk + 1;
     return LZ4R_ERR_CAPACITY;
   }
   if (h[kCtlFail] != ~0ull) return LZ4R_ERR_CORRUPT;
   *out_len = (size_t)h[kCtlLen];
-  return h[kCtlLen] > out_cap ? LZ4R_ERR_CAPACITY : LZ4R_OK;
+  return !nb_out && h[kCtlLen] > out_cap ? LZ4R_ERR_CAPACITY : LZ4R_OK;
 }
 
 // One pass of the bare-stream decode in mode kExact; returns LZ4R_OK, or
@@ -109,9 +113,14 @@ int bare_verdict(const unsigned long long *h, size_t out_cap, size_t *out_len) {
 // for nb_cap and lz4_bare_gate decides on the device whether anything is
 // decoded.  nb_cap 0 (an out_cap far above the stream's possible output): the
 // block count is read back first and sizes both.
+// index (lz4r_stream_index_device): the offsets go to the caller's array of
+// nb_cap entries (0: the count is read back and is the answer), *nb_out takes
+// the block count, and out / out_cap are nullptr / 0: lz4_decode_blocks then
+// checks every block and stores nothing.
 template <bool kExact>
 int bare_pass(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap, const BareScratch &S,
-              size_t nb_cap, size_t *out_len, hipStream_t s) {
+              size_t nb_cap, size_t *out_len, hipStream_t s, uint64_t *index = nullptr,
+              size_t *nb_out = nullptr) {
   const size_t nchunks = S.nchunks;
   const unsigned ng = (unsigned)S.ng;
   hipLaunchKernelGGL(lz4_bare_cand, dim3((unsigned)((nchunks + 3) / 4)), dim3(256), 0, s, in,
@@ -125,7 +134,7 @@ int bare_pass(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap, co
                      S.cnt, S.exitp, S.gsum, S.nmis, S.mis, S.ctl + kCtlStatus, S.lok);
   hipLaunchKernelGGL(lz4_bare_scan, dim3(1), dim3(1024), 0, s, S.gsum, (size_t)ng, S.gbase,
                      S.ctl + kCtlNb);
-  uint64_t *boff = S.boff, *own = nullptr;
+  uint64_t *boff = index ? index : S.boff, *own = nullptr;
   unsigned long long h[kCtlWords] = {};
   if (nb_cap == 0) {
     // no useful bound from out_cap: read the block count (and the status) first
@@ -135,6 +144,10 @@ int bare_pass(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap, co
       return LZ4R_ERR_HIP;
     if (h[kCtlStatus] != 0 || h[kCtlNb] == 0) return LZ4R_ERR_CORRUPT;
     nb_cap = (size_t)h[kCtlNb];
+    if (index) {                                     // no room at all: the count is the answer
+      *nb_out = nb_cap;
+      return LZ4R_ERR_CAPACITY;
+    }
     if (scratch_alloc(reinterpret_cast<void **>(&own), nb_cap * sizeof(uint64_t), s) !=
         hipSuccess)
       return LZ4R_ERR_NOMEM;
@@ -150,7 +163,7 @@ int bare_pass(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_cap, co
   if (hipMemcpyAsync(h, S.ctl, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
     return LZ4R_ERR_HIP;
-  return bare_verdict(h, out_cap, out_len);
+  return bare_verdict(h, out_cap, out_len, nb_out);
 }
 
 }  // namespace
@@ -181,6 +194,37 @@ extern "C" int lz4r_decompress_stream_device(const void *d_in, size_t in_len, vo
   if (rc == LZ4R_ERR_CORRUPT) rc = bare_pass<true>(in, in_len, out, out_cap, S, nb_cap, out_len, s);
   (void)hipFreeAsync(scr, s);
   if (hipStreamSynchronize(s) != hipSuccess) return LZ4R_ERR_HIP;
+  return rc;
+}
+
+extern "C" int lz4r_stream_index_device(const void *d_in, size_t in_len, void *d_block_offsets,
+                                        size_t cap_blocks, size_t *nb, size_t *decoded_len,
+                                        void *stream) {
+  if (!d_in || !d_block_offsets || !nb || !decoded_len ||
+      (reinterpret_cast<uintptr_t>(d_block_offsets) & 7) != 0)
+    return LZ4R_ERR_ARG;
+  *nb = 0;
+  *decoded_len = 0;
+  if (in_len < 9) return LZ4R_ERR_CORRUPT;          // a frame byte and one 8-byte block at least
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const uint8_t *in = static_cast<const uint8_t *>(d_in);
+  uint64_t *index = static_cast<uint64_t *>(d_block_offsets);
+  const size_t nchunks = (in_len - 1 + kChunkB - 1) / kChunkB;
+  // never more entries than the stream can hold blocks (a block is >= 8
+  // bytes): the decoder's grid is sized by them
+  const size_t nb_cap = std::min(cap_blocks, (in_len - 1) / 8 + 1);
+  BareScratch S = bare_scratch_layout(nchunks, 0);  // the offsets array is the caller's
+  uint8_t *scr = nullptr;
+  if (scratch_alloc(reinterpret_cast<void **>(&scr), S.bytes, s) != hipSuccess)
+    return LZ4R_ERR_NOMEM;
+  S.bind(scr);
+  int rc = bare_pass<false>(in, in_len, nullptr, 0, S, nb_cap, decoded_len, s, index, nb);
+  if (rc == LZ4R_ERR_CORRUPT)
+    rc = bare_pass<true>(in, in_len, nullptr, 0, S, nb_cap, decoded_len, s, index, nb);
+  (void)hipFreeAsync(scr, s);
+  if (hipStreamSynchronize(s) != hipSuccess) return LZ4R_ERR_HIP;
+  if (rc != LZ4R_OK) *decoded_len = 0;
+  if (rc != LZ4R_OK && rc != LZ4R_ERR_CAPACITY) *nb = 0;
   return rc;
 }
 

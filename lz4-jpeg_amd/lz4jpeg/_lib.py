@@ -36,6 +36,11 @@ SIGNATURES = [
     ("lz4r_decompress_stream_device", _i, [_vp, _c_size, _vp, _c_size, ctypes.POINTER(_c_size),
                                            _vp]),
     ("lz4r_decompress_stream", _i, [_vp, _c_size, _vp, _c_size, ctypes.POINTER(_c_size)]),
+    ("lz4r_read_items", _c_size, [_c_size]),
+    ("lz4r_read_device", _i, [_vp, _c_size, _vp, _c_size, _vp, _c_size, _c_size, _vp, _c_size,
+                              _vp, _vp]),
+    ("lz4r_stream_index_device", _i, [_vp, _c_size, _vp, _c_size, ctypes.POINTER(_c_size),
+                                      ctypes.POINTER(_c_size), _vp]),
     ("lz4r_check", _i, [_vp, _vp]),
     ("lz4r_set_timing", _i, [_vp, _i]),
     ("lz4r_last_timing", _i, [_vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),

@@ -278,3 +278,128 @@ def decompress_stream(stream_bytes, cap=None):
     if rc != 0:
         _raise(rc, "lz4r_decompress_stream")
     return out[:got.value].tobytes()
+
+
+# -- random access ------------------------------------------------------------
+def stream_index_device(d_stream, length, stream=None):
+    """The block offsets of a bare framed stream (lz4r_stream_index_device):
+    d_stream's first `length` bytes -> (d_offsets int64 tensor, nb,
+    decoded_len), what read_device and decompress_device take.  Tries
+    length // 64 + 64 blocks, then once more with the count the library
+    names.  Raises Lz4Error(-6) on a malformed stream."""
+    import torch
+    cap = length // 64 + 64
+    for _ in range(2):
+        d_offs = torch.empty(cap, dtype=torch.int64, device=d_stream.device)
+        nb, n = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        rc = _lib.lib().lz4r_stream_index_device(
+            ctypes.c_void_p(d_stream.data_ptr()), length, ctypes.c_void_p(d_offs.data_ptr()), cap,
+            ctypes.byref(nb), ctypes.byref(n), _stream_handle(stream))
+        if rc != _lib.LZ4R_ERR_CAPACITY:
+            break
+        cap = nb.value
+    if rc != 0:
+        _raise(rc, "lz4r_stream_index_device")
+    return d_offs[:nb.value], nb.value, n.value
+
+
+def read_items(max_len):
+    """Lanes a read occupies in a call with this max_len (lz4r_read_items)."""
+    return int(_lib.lib().lz4r_read_items(max_len))
+
+
+def read_device(d_stream, length, d_offsets, nb, d_src, d_len, max_len, d_dst=None, d_out=None,
+                out_cap=None, stream=None, check=True):
+    """Many byte ranges of the decoded stream in one call (lz4r_read_device):
+    read r delivers decoded bytes [d_src[r], d_src[r] + d_len[r]) to
+    d_out[d_dst[r] ...].  d_src, d_len, d_dst: int64 tensors on the device;
+    d_offsets as decompress_device takes them; no d_len may exceed max_len
+    (group reads of similar size per call: every read occupies
+    read_items(max_len) lanes).  d_dst=None packs the reads back to back;
+    d_out=None allocates out_cap bytes (default: the reads' furthest end, read
+    back once; nreads * max_len with check=False).  Returns (d_out, d_dst,
+    delivered_bytes); raises Lz4Error(-6) naming the first bad read.
+    check=False does no read-back and returns None for the count."""
+    import torch
+    nreads = d_src.numel()
+    if d_dst is None:
+        d_dst = torch.cumsum(d_len, 0) - d_len
+    if out_cap is None:
+        if d_out is not None:
+            out_cap = d_out.numel()
+        elif check and nreads:
+            out_cap = int((d_dst + d_len).max().item())
+        else:
+            out_cap = nreads * max_len
+    if d_out is None:
+        d_out = torch.empty(max(out_cap, 1), dtype=torch.uint8, device=d_stream.device)
+    if nreads == 0:
+        return d_out, d_dst, (0 if check else None)
+    d_reads = torch.stack((d_src, d_len, d_dst), dim=1).contiguous()
+    res = torch.empty(2, dtype=torch.int64, device=d_stream.device)
+    offs = d_offsets if isinstance(d_offsets, int) else d_offsets.data_ptr()
+    rc = _lib.lib().lz4r_read_device(
+        ctypes.c_void_p(d_stream.data_ptr()), length, ctypes.c_void_p(offs), nb,
+        ctypes.c_void_p(d_reads.data_ptr()), nreads, max_len, ctypes.c_void_p(d_out.data_ptr()),
+        out_cap, ctypes.c_void_p(res.data_ptr()), _stream_handle(stream))
+    if rc != 0:
+        _raise(rc, "lz4r_read_device")
+    if not check:
+        return d_out, d_dst, None
+    if stream is not None:
+        stream.synchronize()          # the result is written on `stream`, not torch's current one
+    n, bad = (int(x) for x in res.cpu().tolist())
+    if bad != -1:
+        raise Lz4Error(_lib.LZ4R_ERR_CORRUPT, f"lz4r_read_device: read {bad - 1}")
+    return d_out, d_dst, n
+
+
+class Reader:
+    """Random access into one compressed stream on the device: the index is
+    built once (stream_index_device) unless the caller has the offsets."""
+
+    def __init__(self, d_stream, length=None, d_offsets=None, nb=None):
+        self.d_stream = d_stream
+        self.length = d_stream.numel() if length is None else length
+        self.decoded_length = None
+        if d_offsets is None:
+            d_offsets, nb, self.decoded_length = stream_index_device(d_stream, self.length)
+        self.d_offsets = d_offsets
+        self.nb = d_offsets.numel() if nb is None else nb
+        if self.decoded_length is None:
+            # the block decoder with no room for output checks every block
+            # and reports the decoded length
+            import torch
+            res = torch.empty(2, dtype=torch.int64, device=d_stream.device)
+            offs = d_offsets if isinstance(d_offsets, int) else d_offsets.data_ptr()
+            rc = _lib.lib().lz4r_decompress_device(
+                ctypes.c_void_p(d_stream.data_ptr()), self.length, ctypes.c_void_p(offs), self.nb,
+                ctypes.c_void_p(res.data_ptr()), 0, ctypes.c_void_p(res.data_ptr()),
+                _stream_handle())
+            if rc != 0:
+                _raise(rc, "lz4r_decompress_device")
+            n, bad = (int(x) for x in res.cpu().tolist())
+            if bad != -1:
+                raise Lz4Error(_lib.LZ4R_ERR_CORRUPT, f"Reader: block {bad - 1}")
+            self.decoded_length = n
+
+    def read(self, src, n):
+        """Decoded bytes [src, src + n) as a uint8 tensor."""
+        import torch
+        if n == 0:
+            return torch.empty(0, dtype=torch.uint8, device=self.d_stream.device)
+        d_src = torch.tensor([src], dtype=torch.int64, device=self.d_stream.device)
+        d_len = torch.tensor([n], dtype=torch.int64, device=self.d_stream.device)
+        d_out, _, got = read_device(self.d_stream, self.length, self.d_offsets, self.nb, d_src,
+                                    d_len, n, out_cap=n)
+        return d_out[:got]
+
+    def read_many(self, d_src, d_len, max_len, **kw):
+        """read_device on this stream: (d_out, d_dst, delivered_bytes)."""
+        import torch
+        if d_src.numel() == 0:
+            return (torch.empty(0, dtype=torch.uint8, device=self.d_stream.device),
+                    torch.empty(0, dtype=torch.int64, device=self.d_stream.device),
+                    0 if kw.get("check", True) else None)
+        return read_device(self.d_stream, self.length, self.d_offsets, self.nb, d_src, d_len,
+                           max_len, **kw)

@@ -314,6 +314,87 @@ int jpegr_stream_encode_device(const void *d_coef, int w, int h, int nimg, int f
                                void *d_out, size_t cap, void *d_out_len,
                                void *d_scratch, void *d_result, void *stream);
 
+/* Random access: many rectangles of a JPR1 or JPT1 stream's images in one
+ * call, each decoded from the tiles it touches and from nothing else.  Tile
+ * records are independent and every tile carries its own Y, Cr and Cb, so a
+ * crop needs only its own tiles' records -- and their offsets, which
+ * jpegr_stream_index_device computes once for any number of crop calls.
+ *
+ * jpegr_stream_index_device: the index scan of pack, unpack and the direct
+ * decode, kept: ntiles + 1 u64 at d_tile_offsets (8-B aligned), entry t the
+ * byte offset of tile t's record from the start of the stream, entry ntiles
+ * the length the header and index imply.  Takes either format.  d_scratch:
+ * jpegr_pack_scratch_bytes(ntiles) bytes, 16-B aligned.  d_result: two u64
+ * (8-B aligned), initialised by the call's own first launch:
+ *   [0] the implied length
+ *   [1] ~0 when the header is a JPR1 or JPT1 header for w, h, nimg and the
+ *       implied length equals in_len; else 0
+ * Asynchronous on `stream`, no host read-back, nothing kept on the host
+ * (capturable).  NULL pointers, bad dimensions, more than 2^32 tiles, a
+ * misaligned d_tile_offsets, d_scratch or d_result: JPEGR_ERR_ARG before any
+ * HIP call.  No read leaves d_in[0, in_len).
+ *
+ * jpegr_crop_device: rectangle r of d_rects[0, nrects) (8-B aligned) is pixels
+ * [x, x + w) x [y, y + h) of image `image`, delivered as RGBA8 rows of 4 w
+ * bytes, back to back, at d_out + dst (d_out 4-B aligned).  It is decoded from
+ * tile columns x / 8 .. (x + w - 1) / 8 and tile rows y / 8 .. (y + h - 1) / 8
+ * of its image only, and its bytes equal that rectangle of what
+ * jpegr_stream_decode_device + jpegr_reconstruct_device(d_rgba_orig = NULL)
+ * give for the image (every tile transformed, alpha 255).
+ * Mapping: every rectangle occupies K = jpegr_crop_items(max_w, max_h) =
+ * (ceil(max_w / 8) + 1) * (ceil(max_h / 8) + 1) items, one per tile that a
+ * max_w x max_h crop can touch at any position, whatever its own size: group
+ * crops of similar size per call, a small crop in a call with a large max_w or
+ * max_h idles most of its items.  nrects * K may not exceed 2^28 (2^22
+ * workgroups of 64 items, one launch): JPEGR_ERR_ARG past that.
+ * d_tile_offsets: jpegr_stream_index_device's, ntiles + 1 u64; caller memory
+ * and not trusted.  d_scratch: jpegr_crop_scratch_bytes(nrects, max_w, max_h)
+ * bytes, 16-B aligned: 256 B x K x nrects of coefficients in rectangle-local
+ * tile grids, then a status word per rectangle (0 on a zero or overflowing
+ * argument).  d_result: three u64 (8-B aligned), reset by the call's own first
+ * launch -- no memset, no tag, no spin:
+ *   [0] the rectangles delivered
+ *   [1] ~0 when every rectangle was delivered, else 1 + the index of the
+ *       first bad rectangle
+ *   [2] the tile records and entropy streams found malformed or rejected among
+ *       the tiles visited (diagnostic: a tile shared by two rectangles counts
+ *       twice, tiles of a rectangle already found bad may go unvisited): this
+ *       call's count, never accumulated
+ * A rectangle is bad when image >= nimg; w > max_w or h > max_h; x + w > the
+ * image's width or y + h > its height; dst is not a multiple of 4; dst + 4 w h
+ * > out_cap (none of the sums wraps); the stream's header is not a JPR1 or
+ * JPT1 header for w, h, nimg (every rectangle is bad then); or a tile it
+ * touches has offsets that are not off[t] <= off[t + 1] <= in_len with a size
+ * of 12 .. 1,036 B, a record the record rules reject, or a stream the entropy
+ * decoder rejects.  w == 0 or h == 0 is a good rectangle that writes nothing,
+ * whatever its other fields say.  Good rectangles are delivered exactly,
+ * whatever the bad ones do.  A rectangle that fails on its own fields or on
+ * the header writes nothing; one that fails inside a tile may leave
+ * unspecified bytes in its own 4 w h output bytes.  Overlapping destination
+ * ranges hold unspecified bytes.
+ * Whatever the stream, the offsets and the rectangles say, no read leaves
+ * d_in[0, in_len), d_tile_offsets[0, ntiles] and d_rects[0, nrects), and no
+ * write leaves d_result, the scratch and each rectangle's own output bytes
+ * within out_cap; table entries and bit bytes are read at byte granularity
+ * inside the checked record, as by jpegr_stream_decode_device.
+ * Asynchronous on `stream`, no host read-back, nothing kept on the host
+ * (capturable); several calls may be in flight at once, each with its own
+ * scratch and result.  JPEGR_ERR_ARG before any HIP call: a NULL pointer; bad
+ * dimensions or more than 2^32 tiles; nrects, max_w or max_h of 0, max_w > w,
+ * max_h > h; in_len < 16; d_rects, d_tile_offsets or d_result not 8-B aligned,
+ * d_scratch not 16-B aligned, d_out not 4-B aligned; nrects * K > 2^28. */
+typedef struct jpegr_rect { uint64_t image, x, y, w, h, dst; } jpegr_rect;
+
+int jpegr_stream_index_device(const void *d_in, size_t in_len, int w, int h, int nimg,
+                              void *d_tile_offsets, void *d_scratch, void *d_result,
+                              void *stream);
+size_t jpegr_crop_items(int max_w, int max_h);
+size_t jpegr_crop_scratch_bytes(size_t nrects, int max_w, int max_h);
+int jpegr_crop_device(const void *d_in, size_t in_len, int w, int h, int nimg,
+                      const void *d_tile_offsets, const void *d_rects, size_t nrects,
+                      int max_w, int max_h, void *d_out, size_t out_cap,
+                      void *d_scratch, void *d_result, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@
 #include <stdlib.h>
 
 #include "jpeg_tables.h"
+#include "jpegr_crop.h"
 #include "../../include/jpegr.h"
 
 #pragma clang fp contract(off)
@@ -505,6 +506,183 @@ __global__ __launch_bounds__(kThreads) void jpeg_recon_kernel(
   }
 }
 
+// ---- crops: jpegr_crop_device's reconstruction half (jpegr_crop.h) -----------
+// jpeg_recon_kernel's phases 1 and 2 as functions, statement for statement (the
+// same tables, products, summation order and round_clamp_u8: bit-exactness
+// rests on that order).  jpeg_recon_kernel itself keeps its body: calling
+// these from it -- both, the IDCT alone, or only the IDCT's summation loops --
+// reorders its instructions and moves its SGPR count (105 -> 97), and its code
+// is not to move.  t: the thread of 256; a strip of up to kTiles
+// tiles, `ntiles` of them live, tile i's 128 int16 at src + 128 i.
+
+// phase 1: coefficients -> dequantised, alpha-scaled doubles in LDS.
+__device__ __forceinline__ void recon_dequant(const int16_t *src, int ntiles, int t,
+                                              double *yac, double *crac, double *cbac) {
+  // Thread t takes the 8 coefficients z0 .. z0 + 7 (z0 = 8 (t mod 16)) of
+  // tiles t / 16 and 16 + t / 16, so its natural indices, quantiser steps and
+  // alpha products are looked up once for both tiles.
+  const int z0 = (t & 15) * 8;
+  const bool luma = z0 < 64;
+  double *const dst = luma ? yac : (z0 < 96 ? crac : cbac);
+  const int stride = luma ? kYStride : kCStride;
+  int nat[8];
+  double qs[8], aa[8];
+  // one load each from z-indexed tables, none depending on another (a
+  // zigzag -> natural lookup followed by the step / alpha loads it indexes
+  // was two dependent memory round trips at the head of every workgroup:
+  // 74.4 -> 64.5 us per 4K image, tools/ab_recon_inproc.py)
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    nat[j] = dRZn[z0 + j];
+    qs[j] = dRZq[z0 + j];
+    aa[j] = dRZa[z0 + j];
+  }
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int tile = k * 16 + (t >> 4);
+    if (tile < ntiles) {
+      const uint4 v = *reinterpret_cast<const uint4 *>(src + tile * 128 + z0);
+      const uint32_t wv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const double q = (double)(int16_t)(wv[j >> 1] >> (16 * (j & 1)));
+        dst[tile * stride + nat[j]] = aa[j] * (q * qs[j]);   // JPEG.c:631-638
+      }
+    }
+  }
+}
+
+// phase 2: IDCT, thread = (tile, x), to the strip's uint8 samples in LDS.
+__device__ __forceinline__ void recon_idct(int t, const double *yac, const double *crac,
+                                           const double *cbac, uint8_t *ys, uint8_t *crs,
+                                           uint8_t *cbs) {
+  const int tile = t >> 3, x = t & 7;
+  double cx[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) cx[u] = dC8[x][u];
+  {
+    const double *a = yac + tile * kYStride;
+    double s[8];
+#pragma unroll
+    for (int y = 0; y < 8; ++y) s[y] = 0.0;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+#pragma unroll
+      for (int v = 0; v < 8; ++v) {
+        const double tv = a[u * 8 + v] * cx[u];                         // (..*c)*cos_x
+#pragma unroll
+        for (int y = 0; y < 8; ++y) s[y] = s[y] + tv * jpegr_tables::C8[y][v];
+      }
+    }
+#pragma unroll
+    for (int y = 0; y < 8; ++y)
+      ys[tile * 64 + x * 8 + y] = (uint8_t)round_clamp_u8(s[y] + 128.0);   // JPEG.c:440
+  }
+#pragma unroll
+  for (int ch = 0; ch < 2; ++ch) {
+    const double *a = (ch == 0 ? crac : cbac) + tile * kCStride;
+    double s[4];
+#pragma unroll
+    for (int y = 0; y < 4; ++y) s[y] = 0.0;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const double tv = a[u * 4 + v] * cx[u];
+#pragma unroll
+        for (int y = 0; y < 4; ++y) s[y] = s[y] + tv * jpegr_tables::C4[y][v];
+      }
+    }
+    uint8_t *dst = (ch == 0 ? crs : cbs) + tile * 32 + x * 4;
+#pragma unroll
+    for (int y = 0; y < 4; ++y) dst[y] = (uint8_t)round_clamp_u8(s[y] + 128.0);
+  }
+}
+
+// A workgroup = a strip of up to kTiles tiles of one tile row of one
+// rectangle's grid; workgroup wg of the call is rectangle wg / (ghm strips),
+// grid row and strip from the remainder (ghm, strips: what a max_w x max_h
+// crop can need).  A rectangle whose status is not good is skipped; the first
+// workgroup of every rectangle counts it into result[0] or names it in
+// result[1].  Phase 3 clips to the rectangle: image pixel (x, row) goes to
+// out + dst + 4 ((row - y) w + (x - x0)).
+__global__ __launch_bounds__(kThreads) void jpeg_crop_recon_kernel(
+    const int16_t *__restrict__ coef, const uint32_t *__restrict__ status,
+    const jpegr_rect *__restrict__ rects, size_t nrects, size_t wg_base, uint32_t gwm,
+    uint32_t ghm, uint32_t strips, uint8_t *__restrict__ out, uint64_t *__restrict__ result) {
+  __shared__ double yac[kTiles * kYStride];
+  __shared__ double crac[kTiles * kCStride];
+  __shared__ double cbac[kTiles * kCStride];
+  __shared__ uint8_t ys[kTiles * 64], crs[kTiles * 32], cbs[kTiles * 32];
+
+  const size_t wg = wg_base + blockIdx.x;
+  const size_t per = (size_t)ghm * strips;
+  const size_t ri = wg / per;
+  if (ri >= nrects) return;
+  const uint32_t rem = (uint32_t)(wg - ri * per);
+  const uint32_t cy = rem / strips, bc0 = (rem - cy * strips) * kTiles;
+  const int t = threadIdx.x;
+  const uint32_t stat = status[ri];
+  if (rem == 0 && t == 0) {
+    if (stat == jpegr_crop::kBad)
+      atomicMin(reinterpret_cast<unsigned long long *>(result + 1), 1ull + (unsigned long long)ri);
+    else
+      atomicAdd(reinterpret_cast<unsigned long long *>(result), 1ull);
+  }
+  if (stat != jpegr_crop::kGood) return;
+  const jpegr_rect rc = rects[ri];
+  const jpegr_crop::Grid g = jpegr_crop::grid_of(rc);
+  if (cy >= g.gh || bc0 >= g.gw) return;
+  const int ntiles = (int)min((uint32_t)kTiles, g.gw - bc0);
+
+  recon_dequant(coef + ((ri * gwm * ghm) + (size_t)cy * g.gw + bc0) * 128, ntiles, t, yac, crac, cbac);
+  __syncthreads();
+  recon_idct(t, yac, crac, cbac, ys, crs, cbs);
+  __syncthreads();
+
+  // ---- phase 3: YCbCr 4:2:2 -> RGB of the pixels inside the rectangle --------
+  {
+    const int r = t >> 5, c = t & 31;
+    const uint64_t row = ((uint64_t)(g.ty0 + cy) << 3) + (uint64_t)r;     // image row
+    if (row < rc.y || row >= rc.y + rc.h) return;
+    uint8_t *const dst = out + rc.dst + (row - rc.y) * rc.w * 4;          // the crop's row
+    const uint64_t sx0 = (uint64_t)(g.tx0 + bc0) << 3;                    // the strip's first column
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      const int lx0 = half * 128 + c * 4;            // pixel column within the strip
+      uint32_t px[4];
+      bool okp[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int lx = lx0 + k, tile = lx >> 3, col = lx & 7;
+        const uint64_t x = sx0 + (uint64_t)lx;
+        okp[k] = tile < ntiles && x >= rc.x && x < rc.x + rc.w;
+        px[k] = 0;
+        if (!okp[k]) continue;
+        const int Y = ys[tile * 64 + r * 8 + col];
+        const int Cr = crs[tile * 32 + r * 4 + (col >> 1)];
+        const int Cb = cbs[tile * 32 + r * 4 + (col >> 1)];
+        const int R = Y + colour_term(1.402f, Cr - 128);            // JPEG.c:601
+        const int G = Y - colour_term(0.344136f, Cb - 128) -
+                      colour_term(0.714136f, Cr - 128);
+        const int B = Y + colour_term(1.772f, Cb - 128);
+        px[k] = (uint32_t)clamp_u8(R) | ((uint32_t)clamp_u8(G) << 8) |
+                ((uint32_t)clamp_u8(B) << 16) | (255u << 24);
+      }
+      // pixel k's dword, addressed only where pixel k is inside
+      const int64_t xo = (int64_t)(sx0 + (uint64_t)lx0) - (int64_t)rc.x;
+      if (okp[0] && okp[3] && ((((uintptr_t)dst + (uint64_t)xo * 4) & 15) == 0)) {
+        *reinterpret_cast<uint4 *>(dst + xo * 4) = make_uint4(px[0], px[1], px[2], px[3]);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (okp[k]) *reinterpret_cast<uint32_t *>(dst + (xo + k) * 4) = px[k];
+      }
+    }
+  }
+}
+
+
 bool g_tables_ready[64] = {false};
 
 hipError_t upload_tables() {
@@ -580,6 +758,21 @@ int launch(bool raw, const void *d_rgba, int w, int h, int nimg, void *d_out,
 }
 
 }  // namespace
+
+int jpegr_crop_recon_launch(const int16_t *d_coef, const uint32_t *d_status,
+                            const jpegr_rect *d_rects, size_t nrects, int max_w, int max_h,
+                            uint8_t *d_out, uint64_t *d_result, hipStream_t st) {
+  if (upload_tables() != hipSuccess) return JPEGR_ERR_HIP;
+  const uint32_t gwm = jpegr_crop::crop_span((uint32_t)max_w), ghm = jpegr_crop::crop_span((uint32_t)max_h);
+  const uint32_t strips = (gwm + kTiles - 1) / kTiles;
+  // at most 2^22 workgroups a launch (HIP's grid limit is 2^32 work-items)
+  const size_t nwg = nrects * ghm * strips, step = (size_t)1 << 22;
+  for (size_t b = 0; b < nwg; b += step)
+    hipLaunchKernelGGL(jpeg_crop_recon_kernel, dim3((unsigned)(nwg - b < step ? nwg - b : step)),
+                       dim3(kThreads), 0, st, d_coef, d_status, d_rects, nrects, b, gwm, ghm, strips,
+                       d_out, d_result);
+  return hipGetLastError() == hipSuccess ? JPEGR_OK : JPEGR_ERR_HIP;
+}
 
 extern "C" {
 

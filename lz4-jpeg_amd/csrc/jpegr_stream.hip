@@ -22,6 +22,14 @@
 //                 cost more in residency than its 16-B staging saved
 //                 (DESIGN 4.9).
 //
+//   jpegr_stream_index_device keeps that scan: jprs_sizes, the scan, and
+//                 jprs_index_finish, which stores every tile's offset
+//   jpegr_crop_device decodes rectangles: jprs_crop_init (the result words,
+//                 every rectangle's status), jprs_crop_decode (jprs_decode's
+//                 shape over the rectangles' cells, records found through the
+//                 caller's offsets), then jpeg_crop_recon_kernel (jpegr.hip);
+//                 the mapping is in jpegr_crop.h, the numbers in DESIGN 4.13
+//
 // The per-stream walk is the slot decoder's (jpegr_decode_common.h:
 // decode_stream / decode_stream_slow, the decode state, the carry-chain
 // compare) over another source of bits: StreamSrc below reads 3-B unaligned
@@ -32,11 +40,15 @@
 #include <stdint.h>
 
 #include "../../include/jpegr.h"
+#include "jpegr_crop.h"
 #include "jpegr_decode_common.h"
 #include "jpegr_pack_common.h"
 
 namespace {
 
+// kThird: the call's result has a third word (the direct decode's count of
+// rejected streams; the index call has two words)
+template <bool kThird>
 __global__ __launch_bounds__(256) void jprs_sizes(const uint8_t *__restrict__ in, uint64_t in_len,
                                                   size_t ntiles, size_t t_base, uint32_t w,
                                                   uint32_t h, uint32_t nimg,
@@ -47,7 +59,7 @@ __global__ __launch_bounds__(256) void jprs_sizes(const uint8_t *__restrict__ in
   tsz[t] = get_index(in, in_len, t);
   if (t == 0) {
     result[1] = header_ok(in, in_len, ntiles, w, h, nimg, true) ? ~0ull : 0ull;
-    result[2] = 0ull;
+    if constexpr (kThird) result[2] = 0ull;
   }
 }
 
@@ -189,28 +201,56 @@ __device__ __forceinline__ uint32_t stream_decode_wave(DecLds<kLuma ? 64 : 32, k
   return fails;
 }
 
+// Where decode_record reports.  malformed(t): the luma wave's lane, its record
+// (tile t of the stream) fails the record rule; rejected(fails, lane): every
+// lane of a wave, with the lane's rejected streams.
+// The direct decode: the first malformed tile into result[1], the wave's
+// rejected streams in one add to result[2], after jprs_sizes' zero in stream
+// order.
+struct RangeReport {
+  uint64_t *__restrict__ result;
+  __device__ __forceinline__ void malformed(size_t t) const {
+    atomicMin(reinterpret_cast<unsigned long long *>(result + 1), 1ull + (unsigned long long)t);
+  }
+  __device__ __forceinline__ void rejected(uint32_t fails, int lane) const {
+    const uint32_t f = wave_rejected(fails);
+    if (f && lane == __builtin_ctzll(__ballot(1)))
+      atomicAdd(reinterpret_cast<unsigned long long *>(result + 2), (unsigned long long)f);
+  }
+};
+// A crop: either failure turns the lane's rectangle bad (stat: its status
+// word) and is counted into result[2], after jprs_crop_init's zero.
+struct CropReport {
+  uint64_t *__restrict__ result;
+  uint32_t *stat;
+  __device__ __forceinline__ void malformed(size_t) const {
+    *stat = jpegr_crop::kBad;
+    atomicAdd(reinterpret_cast<unsigned long long *>(result + 2), 1ull);
+  }
+  __device__ __forceinline__ void rejected(uint32_t fails, int lane) const {
+    if (fails) *stat = jpegr_crop::kBad;
+    RangeReport{result}.rejected(fails, lane);
+  }
+};
+
 // A lane's record of `size` bytes at rec, tile t of the stream: checked by
 // the rule every reader shares (record_rule, jpegr_pack_common.h), whose reads
 // stay inside the record; then the wave's channel group is decoded.
-template <bool kTight>
+template <bool kTight, typename Report>
 __device__ __forceinline__ void decode_record(DecLds<64, kFastCap> &SY, DecLds<32, kChromaCap> &SC,
                                               int lane, int wv, const uint8_t *rec, uint32_t size,
-                                              size_t t, uint64_t *__restrict__ result,
+                                              size_t t, const Report rep,
                                               int16_t *__restrict__ tile_out) {
   uint32_t so[3] = {0u, 0u, 0u}, m[3] = {0u, 0u, 0u}, md = 0u;
   const bool good = record_rule<kTight>([&](uint32_t x) -> uint32_t { return rec[x]; }, 0u, size, so, m, md);
   uint32_t fails;
   if (__builtin_amdgcn_readfirstlane(wv) == 0) {
-    if (!good)
-      atomicMin(reinterpret_cast<unsigned long long *>(result + 1), 1ull + (unsigned long long)t);
+    if (!good) rep.malformed(t);
     fails = stream_decode_wave<true, kTight>(SY, lane, rec, good, so, m, md, tile_out);
   } else {
     fails = stream_decode_wave<false, kTight>(SC, lane, rec, good, so, m, md, tile_out);
   }
-  // the wave's rejected streams: one add, after jprs_sizes' zero in stream order
-  const uint32_t f = wave_rejected(fails);
-  if (f && lane == __builtin_ctzll(__ballot(1)))
-    atomicAdd(reinterpret_cast<unsigned long long *>(result + 2), (unsigned long long)f);
+  rep.rejected(fails, lane);
 }
 
 __global__ __launch_bounds__(2 * kLanes) void jprs_decode(
@@ -251,9 +291,102 @@ __global__ __launch_bounds__(2 * kLanes) void jprs_decode(
   int16_t *const tile_out = wg_out + (size_t)lane * 128;
   // the stream's format, from the header jprs_sizes accepted: one for the launch
   if (__builtin_amdgcn_readfirstlane(fmt) == 'T')
-    decode_record<true>(SY, SC, lane, wv, rec, size, a + lane, result, tile_out);
+    decode_record<true>(SY, SC, lane, wv, rec, size, a + lane, RangeReport{result}, tile_out);
   else
-    decode_record<false>(SY, SC, lane, wv, rec, size, a + lane, result, tile_out);
+    decode_record<false>(SY, SC, lane, wv, rec, size, a + lane, RangeReport{result}, tile_out);
+}
+
+// ---- the index, kept (jpegr_stream_index_device) ----------------------------------
+
+// A workgroup (one wave) per scan group: group_offsets' 64 offsets, stored; the
+// last group stores the total too.  The verdict: jprs_sizes' header verdict in
+// result[1], cleared here when the implied length (the scan's, result[0]) is
+// not in_len.
+__global__ __launch_bounds__(kGT) void jprs_index_finish(
+    const uint32_t *__restrict__ tsz, const uint32_t *__restrict__ gsum,
+    const uint64_t *__restrict__ part, size_t ntiles, size_t g_base, uint64_t in_len,
+    uint64_t *__restrict__ result, uint64_t *__restrict__ toff_out) {
+  __shared__ uint64_t toff[kGT + 1];
+  const int tid = threadIdx.x;
+  const size_t g = g_base + blockIdx.x, g0 = g * kGT;
+  if (g0 >= ntiles) return;
+  group_offsets(tid, g, ntiles, tsz, gsum, part, toff);
+  __syncthreads();
+  const int nt = (int)min((size_t)kGT, ntiles - g0);
+  if (tid < nt) toff_out[g0 + tid] = toff[tid];
+  if (tid == 0 && g0 + nt == ntiles) toff_out[ntiles] = toff[nt];   // lanes past nt added 0
+  if (tid == 0 && g == 0 && result[0] != in_len) result[1] = 0ull;
+}
+
+// ---- crops (jpegr_crop_device; the mapping: jpegr_crop.h) ----------------------------
+
+// The call's first launch: resets the result words and gives every rectangle
+// its status from its own fields and the header (none of the sums can wrap:
+// each is a comparison against what is left).
+__global__ __launch_bounds__(256) void jprs_crop_init(
+    const uint8_t *__restrict__ in, uint64_t in_len, size_t ntiles, uint32_t w, uint32_t h,
+    uint32_t nimg, const jpegr_rect *__restrict__ rects, size_t nrects, size_t r_base,
+    uint32_t max_w, uint32_t max_h, uint64_t out_cap, uint32_t *__restrict__ status,
+    uint64_t *__restrict__ result) {
+  const size_t r = r_base + (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (r == 0) {
+    result[0] = 0ull;
+    result[1] = ~0ull;
+    result[2] = 0ull;
+  }
+  if (r >= nrects) return;
+  const jpegr_rect rc = rects[r];
+  uint32_t st = jpegr_crop::kGood;
+  if (!header_ok(in, in_len, ntiles, w, h, nimg, true))
+    st = jpegr_crop::kBad;
+  else if (rc.w == 0 || rc.h == 0)
+    st = jpegr_crop::kEmpty;
+  else if (rc.image >= nimg || rc.w > max_w || rc.h > max_h || rc.x > w || rc.w > w - rc.x ||
+           rc.y > h || rc.h > h - rc.y || (rc.dst & 3) != 0 || rc.dst > out_cap ||
+           4 * rc.w * rc.h > out_cap - rc.dst)         // w, h < 2^31: the product cannot wrap
+    st = jpegr_crop::kBad;
+  status[r] = st;
+}
+
+// jprs_decode's shape -- 64 items a workgroup, a luma wave and a chroma wave --
+// over the rectangles' cells: item i is cell i % K of rectangle i / K.  A lane
+// finds its record through toff, the caller's offsets, which are not trusted:
+// the record must lie in the stream and have a record's size before a byte of
+// it is read; decode_record then reads inside it only.  The ints go to the
+// item's 128 int16 of the scratch.
+__global__ __launch_bounds__(2 * kLanes) void jprs_crop_decode(
+    const uint8_t *__restrict__ in, uint64_t in_len, uint32_t tiles_x, uint32_t tiles_y,
+    const uint64_t *__restrict__ toff, const jpegr_rect *__restrict__ rects, size_t nrects,
+    uint32_t K, size_t wg_base, uint32_t *status, uint64_t *__restrict__ result,
+    int16_t *__restrict__ coef) {
+  __shared__ DecLds<64, kFastCap> SY;
+  __shared__ DecLds<32, kChromaCap> SC;
+  const int tid = threadIdx.x, lane = tid & (kLanes - 1), wv = tid >> 6;
+  const size_t i = (wg_base + blockIdx.x) * kLanes + lane;
+  const size_t r = i / K;
+  if (r >= nrects) return;
+  const uint32_t cell = (uint32_t)(i - r * K);
+  uint32_t *const stat = status + r;
+  if (*stat != jpegr_crop::kGood) return;            // bad on its own fields, empty, or a tile failed
+  const jpegr_rect rc = rects[r];
+  const jpegr_crop::Grid g = jpegr_crop::grid_of(rc);
+  if ((uint64_t)cell >= (uint64_t)g.gw * g.gh) return;   // an idle cell
+  const uint32_t cy = cell / g.gw, cx = cell - cy * g.gw;
+  // inside the image (jprs_crop_init): t < ntiles, so toff[t + 1] is the caller's
+  const size_t t = (rc.image * tiles_y + g.ty0 + cy) * tiles_x + g.tx0 + cx;
+  const uint64_t o0 = toff[t], o1 = toff[t + 1];
+  if (!(o0 <= o1 && o1 <= in_len && o1 - o0 >= 12u && o1 - o0 <= (uint64_t)kRecMax)) {
+    if (wv == 0) CropReport{result, stat}.malformed(t);
+    return;
+  }
+  const uint8_t *rec = in + o0;
+  const uint32_t size = (uint32_t)(o1 - o0);
+  int16_t *const tile_out = coef + i * 128;
+  const uint32_t fmt = in[2];                         // 'R' or 'T': the header jprs_crop_init accepted
+  if (__builtin_amdgcn_readfirstlane(fmt) == 'T')
+    decode_record<true>(SY, SC, lane, wv, rec, size, t, CropReport{result, stat}, tile_out);
+  else
+    decode_record<false>(SY, SC, lane, wv, rec, size, t, CropReport{result, stat}, tile_out);
 }
 }  // namespace
 
@@ -272,7 +405,7 @@ extern "C" int jpegr_stream_decode_device(const void *d_in, size_t in_len, int w
   auto *in = static_cast<const uint8_t *>(d_in);
   auto *result = static_cast<uint64_t *>(d_result);
   launch_chunks(ntiles, 256, [&](size_t b, unsigned n) {
-    hipLaunchKernelGGL(jprs_sizes, dim3(n), dim3(256), 0, st, in, (uint64_t)in_len, ntiles, b * 256,
+    hipLaunchKernelGGL(jprs_sizes<true>, dim3(n), dim3(256), 0, st, in, (uint64_t)in_len, ntiles, b * 256,
                        (uint32_t)w, (uint32_t)h, (uint32_t)nimg, s.tsz, result);
   });
   scan(s, ntiles, result, st);
@@ -281,4 +414,77 @@ extern "C" int jpegr_stream_decode_device(const void *d_in, size_t in_len, int w
                        ntile, b, s.tsz, s.gsum, s.part, result, static_cast<int16_t *>(d_coef));
   });
   return hipGetLastError() == hipSuccess ? JPEGR_OK : JPEGR_ERR_HIP;
+}
+
+extern "C" int jpegr_stream_index_device(const void *d_in, size_t in_len, int w, int h, int nimg,
+                                         void *d_tile_offsets, void *d_scratch, void *d_result,
+                                         void *stream) {
+  const size_t ntiles = tiles_of(w, h, nimg);
+  if (!d_in || !d_tile_offsets || !d_scratch || !d_result || ntiles == 0 ||
+      (reinterpret_cast<uintptr_t>(d_tile_offsets) & 7) != 0 ||
+      (reinterpret_cast<uintptr_t>(d_result) & 7) != 0 ||
+      (reinterpret_cast<uintptr_t>(d_scratch) & 15) != 0)
+    return JPEGR_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const Scratch s = scratch_of(d_scratch, ntiles);
+  auto *in = static_cast<const uint8_t *>(d_in);
+  auto *result = static_cast<uint64_t *>(d_result);
+  launch_chunks(ntiles, 256, [&](size_t b, unsigned n) {
+    hipLaunchKernelGGL(jprs_sizes<false>, dim3(n), dim3(256), 0, st, in, (uint64_t)in_len, ntiles, b * 256,
+                       (uint32_t)w, (uint32_t)h, (uint32_t)nimg, s.tsz, result);
+  });
+  scan(s, ntiles, result, st);
+  launch_chunks(ntiles, kGT, [&](size_t b, unsigned n) {
+    hipLaunchKernelGGL(jprs_index_finish, dim3(n), dim3(kGT), 0, st, s.tsz, s.gsum, s.part, ntiles, b,
+                       (uint64_t)in_len, result, static_cast<uint64_t *>(d_tile_offsets));
+  });
+  return hipGetLastError() == hipSuccess ? JPEGR_OK : JPEGR_ERR_HIP;
+}
+
+extern "C" size_t jpegr_crop_items(int max_w, int max_h) {
+  if (max_w <= 0 || max_h <= 0) return 0;
+  return (size_t)jpegr_crop::crop_span((uint32_t)max_w) * jpegr_crop::crop_span((uint32_t)max_h);
+}
+
+// [256 B x K x nrects of coefficients][u32 status x nrects], whole 16-B chunks
+extern "C" size_t jpegr_crop_scratch_bytes(size_t nrects, int max_w, int max_h) {
+  const size_t K = jpegr_crop_items(max_w, max_h);
+  if (nrects == 0 || K == 0 || K > SIZE_MAX / 512 || nrects > (SIZE_MAX - 15) / (256 * K + 4)) return 0;
+  return (nrects * (256 * K + 4) + 15) & ~(size_t)15;
+}
+
+extern "C" int jpegr_crop_device(const void *d_in, size_t in_len, int w, int h, int nimg,
+                                 const void *d_tile_offsets, const void *d_rects, size_t nrects,
+                                 int max_w, int max_h, void *d_out, size_t out_cap,
+                                 void *d_scratch, void *d_result, void *stream) {
+  const size_t ntiles = tiles_of(w, h, nimg);
+  const size_t K = jpegr_crop_items(max_w, max_h);
+  if (!d_in || !d_tile_offsets || !d_rects || !d_out || !d_scratch || !d_result || ntiles == 0 ||
+      nrects == 0 || K == 0 || max_w > w || max_h > h || in_len < (size_t)kHdr ||
+      (reinterpret_cast<uintptr_t>(d_rects) & 7) != 0 ||
+      (reinterpret_cast<uintptr_t>(d_tile_offsets) & 7) != 0 ||
+      (reinterpret_cast<uintptr_t>(d_result) & 7) != 0 ||
+      (reinterpret_cast<uintptr_t>(d_scratch) & 15) != 0 ||
+      (reinterpret_cast<uintptr_t>(d_out) & 3) != 0 ||
+      nrects > kMaxWg * kLanes / K)                   // one launch_chunks pass: 2^28 items
+    return JPEGR_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  auto *in = static_cast<const uint8_t *>(d_in);
+  auto *rects = static_cast<const jpegr_rect *>(d_rects);
+  auto *result = static_cast<uint64_t *>(d_result);
+  auto *coef = static_cast<int16_t *>(d_scratch);
+  auto *status = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_scratch) + nrects * K * 256);
+  launch_chunks(nrects, 256, [&](size_t b, unsigned n) {
+    hipLaunchKernelGGL(jprs_crop_init, dim3(n), dim3(256), 0, st, in, (uint64_t)in_len, ntiles,
+                       (uint32_t)w, (uint32_t)h, (uint32_t)nimg, rects, nrects, b * 256,
+                       (uint32_t)max_w, (uint32_t)max_h, (uint64_t)out_cap, status, result);
+  });
+  launch_chunks(nrects * K, kLanes, [&](size_t b, unsigned n) {
+    hipLaunchKernelGGL(jprs_crop_decode, dim3(n), dim3(2 * kLanes), 0, st, in, (uint64_t)in_len,
+                       (uint32_t)((w + 7) / 8), (uint32_t)((h + 7) / 8),
+                       static_cast<const uint64_t *>(d_tile_offsets), rects, nrects, (uint32_t)K, b,
+                       status, result, coef);
+  });
+  return jpegr_crop_recon_launch(coef, status, rects, nrects, max_w, max_h,
+                                 static_cast<uint8_t *>(d_out), result, st);
 }

@@ -69,6 +69,11 @@ SIGNATURES = [
                                  ctypes.POINTER(_i)]),
     ("jpegr_stream_encode_scratch_bytes", _c_size, [_c_size, _c_size]),
     ("jpegr_stream_encode_device", _i, [_vp, _i, _i, _i, _i, _vp, _c_size, _vp, _vp, _vp, _vp]),
+    ("jpegr_stream_index_device", _i, [_vp, _c_size, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    ("jpegr_crop_items", _c_size, [_i, _i]),
+    ("jpegr_crop_scratch_bytes", _c_size, [_c_size, _i, _i]),
+    ("jpegr_crop_device", _i, [_vp, _c_size, _i, _i, _i, _vp, _vp, _c_size, _i, _i, _vp, _c_size,
+                               _vp, _vp, _vp]),
     ("jpegr_planes_device", _i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     ("jpegr_dct_blocks_device", _i, [_vp, _i, _i, _i, _vp, _vp]),
     ("jpegr_quantize_device", _i, [_vp, _vp, _i, _c_size, _vp]),

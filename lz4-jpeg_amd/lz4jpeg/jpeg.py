@@ -304,6 +304,141 @@ def decompress_images_device(d_stream, first=0, count=None):
     return out, w, h, count
 
 
+# -- random access ------------------------------------------------------------
+def stream_index_device(d_stream, in_len, w, h, nimg=1, d_offsets=None, d_result=None, scratch=None,
+                        stream=None):
+    """The tile offsets of a JPR1 or JPT1 stream's first in_len bytes
+    (jpegr_stream_index_device), what crop_device takes.  Returns (d_offsets,
+    d_result): d_offsets int64, nimg * tiles(w, h) + 1 entries, entry t the
+    byte offset of tile t's record and the last one the length the header and
+    index imply; d_result two int64 on the device, [0] that length, [1] -1 (all
+    ones) when the header is these dimensions' and the length is in_len, else
+    0.  Asynchronous: no read-back."""
+    import torch
+    nt = nimg * tiles(w, h)
+    if in_len > d_stream.numel():
+        raise ValueError("in_len past the end of d_stream")
+    if d_offsets is None:
+        d_offsets = torch.empty(nt + 1, dtype=torch.int64, device=d_stream.device)
+    elif d_offsets.numel() < nt + 1:
+        raise ValueError("d_offsets smaller than ntiles + 1")
+    if d_result is None:
+        d_result = torch.empty(2, dtype=torch.int64, device=d_stream.device)
+    if scratch is None:
+        scratch = _pack_scratch(nt, d_stream.device)
+    rc = _lib.lib().jpegr_stream_index_device(
+        ctypes.c_void_p(d_stream.data_ptr()), in_len, w, h, nimg,
+        ctypes.c_void_p(d_offsets.data_ptr()), ctypes.c_void_p(scratch.data_ptr()),
+        ctypes.c_void_p(d_result.data_ptr()), _stream_handle(stream))
+    if rc != 0:
+        raise JpegError(rc, "jpegr_stream_index_device")
+    return d_offsets, d_result
+
+
+def crop_items(max_w, max_h):
+    """Items a crop occupies in a call with these maxima (jpegr_crop_items)."""
+    return int(_lib.lib().jpegr_crop_items(max_w, max_h))
+
+
+def crop_scratch_bytes(nrects, max_w, max_h):
+    return int(_lib.lib().jpegr_crop_scratch_bytes(nrects, max_w, max_h))
+
+
+def crop_device(d_stream, in_len, w, h, nimg, d_offsets, d_image, d_x, d_y, d_w, d_h, max_w, max_h,
+                d_dst=None, d_out=None, out_cap=None, scratch=None, d_result=None, stream=None,
+                check=True):
+    """Many rectangles of a stream's images in one call (jpegr_crop_device):
+    crop r delivers pixels [d_x[r], d_x[r] + d_w[r]) x [d_y[r], d_y[r] + d_h[r])
+    of image d_image[r] as RGBA8 rows to d_out[d_dst[r] ...], each decoded from
+    the tiles it touches only.  d_image .. d_h, d_dst: int64 tensors on the
+    device; d_offsets: stream_index_device's; no d_w may exceed max_w, no d_h
+    max_h (group crops of similar size per call: every crop occupies
+    crop_items(max_w, max_h) items).  d_dst=None packs the crops back to back
+    at 4 w h bytes each; d_out=None allocates out_cap bytes (default: the
+    crops' furthest end, read back once; nrects * 4 max_w max_h with
+    check=False).  Returns (d_out, d_dst, delivered); raises JpegError naming
+    the first bad rectangle.  check=False does no read-back and returns None
+    for the count."""
+    import torch
+    nrects = d_x.numel()
+    if d_dst is None:
+        d_len = 4 * d_w * d_h
+        d_dst = torch.cumsum(d_len, 0) - d_len
+    if out_cap is None:
+        if d_out is not None:
+            out_cap = d_out.numel()
+        elif check and nrects:
+            out_cap = int((d_dst + 4 * d_w * d_h).max().item())
+        else:
+            out_cap = nrects * 4 * max_w * max_h
+    if d_out is None:
+        d_out = torch.empty(max(out_cap, 4), dtype=torch.uint8, device=d_stream.device)
+    if nrects == 0:
+        return d_out, d_dst, (0 if check else None)
+    if in_len > d_stream.numel():
+        raise ValueError("in_len past the end of d_stream")
+    if d_offsets.numel() < nimg * tiles(w, h) + 1:
+        raise ValueError("d_offsets smaller than ntiles + 1")
+    d_rects = torch.stack((d_image, d_x, d_y, d_w, d_h, d_dst), dim=1).contiguous()
+    need = crop_scratch_bytes(nrects, max_w, max_h)
+    if scratch is None:
+        scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=d_stream.device)
+    elif scratch.numel() < need:
+        raise ValueError("scratch smaller than crop_scratch_bytes(nrects, max_w, max_h)")
+    if d_result is None:
+        d_result = torch.empty(3, dtype=torch.int64, device=d_stream.device)
+    rc = _lib.lib().jpegr_crop_device(
+        ctypes.c_void_p(d_stream.data_ptr()), in_len, w, h, nimg,
+        ctypes.c_void_p(d_offsets.data_ptr()), ctypes.c_void_p(d_rects.data_ptr()), nrects,
+        max_w, max_h, ctypes.c_void_p(d_out.data_ptr()), out_cap,
+        ctypes.c_void_p(scratch.data_ptr()), ctypes.c_void_p(d_result.data_ptr()),
+        _stream_handle(stream))
+    if rc != 0:
+        raise JpegError(rc, "jpegr_crop_device")
+    if not check:
+        return d_out, d_dst, None
+    if stream is not None:
+        stream.synchronize()          # the result is written on `stream`, not torch's current one
+    n, bad, _ = (int(x) for x in d_result.cpu().tolist())
+    if bad != -1:
+        raise JpegError(-1, f"jpegr_crop_device: rectangle {bad - 1}")
+    return d_out, d_dst, n
+
+
+class StreamReader:
+    """Random access into one JPR1 or JPT1 stream on the device (a uint8
+    tensor, exactly the stream): the header is read back once and the index is
+    built once (stream_index_device).  Raises JpegError on a stream whose
+    header or index is inconsistent."""
+
+    def __init__(self, d_stream):
+        if d_stream.numel() < 16:
+            raise JpegError(-1, "StreamReader: shorter than a header")
+        self.d_stream = d_stream
+        self.length = d_stream.numel()
+        self.w, self.h, self.nimg, self.tight = stream_format(d_stream[:16].cpu().numpy().tobytes())
+        self.d_offsets, d_result = stream_index_device(d_stream, self.length, self.w, self.h,
+                                                       self.nimg)
+        verdict = int(d_result[1].item())
+        if verdict != -1:
+            raise JpegError(-1, f"StreamReader: inconsistent stream (verdict {verdict})")
+
+    def crop(self, image, x, y, w, h):
+        """Pixels [x, x + w) x [y, y + h) of image `image`: a uint8 tensor (h, w, 4)."""
+        import torch
+        dev = self.d_stream.device
+        if w == 0 or h == 0:
+            return torch.empty((h, w, 4), dtype=torch.uint8, device=dev)
+        one = [torch.tensor([v], dtype=torch.int64, device=dev) for v in (image, x, y, w, h)]
+        d_out, _, _ = self.crops(*one, min(w, self.w), min(h, self.h), out_cap=4 * w * h)
+        return d_out[:4 * w * h].view(h, w, 4)
+
+    def crops(self, d_image, d_x, d_y, d_w, d_h, max_w, max_h, **kw):
+        """crop_device on this stream: (d_out, d_dst, delivered)."""
+        return crop_device(self.d_stream, self.length, self.w, self.h, self.nimg, self.d_offsets,
+                           d_image, d_x, d_y, d_w, d_h, max_w, max_h, **kw)
+
+
 def stream_encode_scratch_bytes(ntiles, cap):
     return int(_lib.lib().jpegr_stream_encode_scratch_bytes(ntiles, cap))
 

@@ -5,7 +5,8 @@ settle() on each measured call, then event-timed means over back-to-back
 launches.
 
     python tools/jpeg_pack_bench.py [--steps K] [--once N]
-                                    [--decode | --tight [--against LIB] | --direct [--against LIB]]
+                                    [--decode | --tight [--against LIB] | --direct [--against LIB]
+                                     | --crop]
 
 Images: bench.py's 3840x2160 random image (synth.rand_rgba_device, seed 1)
 and a 3840x2160 smooth one (tests/test_gpu_entropy.py's generator).  Prints
@@ -44,7 +45,20 @@ against the two-stage stream.  --against LIB adds the second build's entropy
 encode / decode, both packs, both direct encodes and the direct decode to the
 same rounds, with the ratio of the medians per pair.  Then the device memory
 compress_device peaks at, direct or not, for one image and for eight.  With
---once N: N direct encodes of each format per image and nothing else."""
+--once N: N direct encodes of each format per image and nothing else.
+
+--crop: random access (jpegr_stream_index_device + jpegr_crop_device), for
+profiles/jpr_crop_bench.md: a stream of 16 images of 1920x1080, random and
+smooth, JPR1 and JPT1, and 256 uniformly random 224x224 crops of it through
+crop_device with the index built once outside the timed call, and with the
+index call inside it; beside them what there was before: the direct decode and
+reconstruction of all 16 images followed by a torch gather of the same
+rectangles.  Then one rectangle per image covering the whole image against
+decode + reconstruct of the same images: the price of the crop mapping where
+it has nothing to save.  All in this run after the same pre-warm and settle,
+alternated over --rounds rounds, event-timed; the crops' bytes are checked
+against the gather's.  With --once N: N crop calls per stream and nothing
+else."""
 import argparse
 import json
 import os
@@ -493,6 +507,118 @@ def direct_side(args, torch, jpeg, name, img, d_coef, other):
     print(json.dumps(mem), flush=True)
 
 
+CW, CH, CN = 1920, 1080, 16                  # --crop: the stream's images
+CROP, NCROPS = 224, 256
+
+
+def crop_side(args, torch, jpeg, synth, dev):
+    """Crops straight from the stream beside decode-everything-and-gather."""
+    nt = CN * jpeg.tiles(CW, CH)
+    px = CW * CH
+    rng = np.random.default_rng(7)
+    im = rng.integers(0, CN, NCROPS)
+    x = rng.integers(0, CW - CROP + 1, NCROPS)
+    y = rng.integers(0, CH - CROP + 1, NCROPS)
+    touched = int((((x + CROP - 1) // 8 - x // 8 + 1) * ((y + CROP - 1) // 8 - y // 8 + 1)).sum())
+    t64 = lambda a: torch.from_numpy(np.asarray(a, np.int64)).to(dev)
+    full_w, full_h = t64(np.full(NCROPS, CROP)), t64(np.full(NCROPS, CROP))
+    cols = [t64(im), t64(x), t64(y), full_w, full_h]
+    d_dst = t64(np.arange(NCROPS) * 4 * CROP * CROP)
+    cap = NCROPS * 4 * CROP * CROP
+    # the gather's pixel numbers: crop r's row j, column i
+    jj, ii = np.mgrid[0:CROP, 0:CROP]
+    d_idx = t64(((im * px + y * CW + x)[:, None, None] + jj[None] * CW + ii[None]).reshape(-1))
+    whole = [t64(np.arange(CN)), t64(np.zeros(CN)), t64(np.zeros(CN)), t64(np.full(CN, CW)),
+             t64(np.full(CN, CH))]
+    d_wdst = t64(np.arange(CN) * 4 * px)
+    images = {}
+    d_img = torch.empty(CN * px * 4, dtype=torch.uint8, device=dev)
+    synth.rand_rgba_device(d_img, 0, CN * px, seed=1)
+    images["random"] = d_img
+    images["smooth"] = torch.from_numpy(smooth_image(CW, CH)).to(dev).reshape(-1).repeat(CN)
+    d_offs = torch.empty(nt + 1, dtype=torch.int64, device=dev)
+    d_ires = torch.empty(2, dtype=torch.int64, device=dev)
+    d_res, d_wres = (torch.empty(3, dtype=torch.int64, device=dev) for _ in range(2))
+    d_res3 = torch.empty(3, dtype=torch.int64, device=dev)
+    iscr = torch.empty(int(jpeg._lib.lib().jpegr_pack_scratch_bytes(nt)), dtype=torch.uint8, device=dev)
+    cscr_bytes = jpeg.crop_scratch_bytes(NCROPS, CROP, CROP)
+    wscr_bytes = jpeg.crop_scratch_bytes(CN, CW, CH)
+    cscr = torch.empty(max(cscr_bytes, wscr_bytes), dtype=torch.uint8, device=dev)
+    d_out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    d_wout = torch.empty(CN * px * 4, dtype=torch.uint8, device=dev)
+    d_coef = torch.empty(nt * 128, dtype=torch.int16, device=dev)
+    for name, img in images.items():
+        for tight in (False, True):
+            d_stream = jpeg.compress_device(img, CW, CH, CN, tight=tight)
+            n = d_stream.numel()
+
+            def index():
+                jpeg.stream_index_device(d_stream, n, CW, CH, CN, d_offsets=d_offs, d_result=d_ires,
+                                         scratch=iscr)
+
+            def crops():
+                jpeg.crop_device(d_stream, n, CW, CH, CN, d_offs, *cols, CROP, CROP, d_dst=d_dst,
+                                 d_out=d_out, out_cap=cap, scratch=cscr, d_result=d_res, check=False)
+
+            def index_and_crops():
+                index()
+                crops()
+
+            def decode_all():
+                jpeg.decode_stream_device(d_stream, n, CW, CH, CN, d_coef=d_coef, d_result=d_res3,
+                                          scratch=iscr)
+                return jpeg.reconstruct_device(d_coef, CW, CH, CN)
+
+            def decode_all_and_gather():
+                return decode_all().view(torch.int32)[d_idx]
+
+            def whole_crops():
+                jpeg.crop_device(d_stream, n, CW, CH, CN, d_offs, *whole, CW, CH, d_dst=d_wdst,
+                                 d_out=d_wout, out_cap=d_wout.numel(), scratch=cscr, d_result=d_wres,
+                                 check=False)
+
+            index()
+            if args.once:
+                for _ in range(args.once):
+                    crops()
+                torch.cuda.synchronize()
+                continue
+            crops()
+            got = d_out.clone()
+            want = decode_all_and_gather()
+            whole_crops()
+            torch.cuda.synchronize()
+            ok = bool(torch.equal(got.view(torch.int32), want)) \
+                and bool(torch.equal(d_wout, decode_all())) \
+                and d_ires.cpu().tolist() == [n, -1] and d_res.cpu().tolist() == [NCROPS, -1, 0] \
+                and d_wres.cpu().tolist() == [CN, -1, 0] and d_res3.cpu().tolist() == [n, -1, 0]
+            del got, want
+            res = {"stream": f"{name} {CN} x {CW}x{CH} {'JPT1' if tight else 'JPR1'}", "tiles": nt,
+                   "stream_bytes": n, "crops": f"{NCROPS} of {CROP}x{CROP}", "tiles_touched": touched,
+                   "touched_fraction": round(touched / nt, 4), "outputs_equal": ok,
+                   "steps": args.steps, "rounds": args.rounds,
+                   "crop_items": jpeg.crop_items(CROP, CROP), "crop_scratch_bytes": cscr_bytes,
+                   "whole_items": jpeg.crop_items(CW, CH), "whole_scratch_bytes": wscr_bytes,
+                   "decode_all_coef_bytes": nt * 256, "decode_all_rgba_bytes": CN * px * 4}
+            calls = [("index", index), ("crops", crops), ("index_and_crops", index_and_crops),
+                     ("decode_all_and_gather", decode_all_and_gather), ("whole_crops", whole_crops),
+                     ("decode_all", decode_all)]
+            ms = {k: [] for k, _ in calls}
+            for r in range(args.rounds):                  # alternated; the order turns with the round
+                for key, fn in calls[r % len(calls):] + calls[:r % len(calls)]:
+                    settle(fn, torch.cuda.synchronize, chunk=4)
+                    ms[key].append(timed(fn, args.steps, torch))
+            for key, _ in calls:
+                res[key + "_ms"] = spread(ms[key])
+            med = lambda k: res[k + "_ms"]["median"]
+            res["crops_over_decode_all_and_gather"] = round(med("crops") / med("decode_all_and_gather"), 4)
+            res["index_and_crops_over_decode_all_and_gather"] = round(
+                med("index_and_crops") / med("decode_all_and_gather"), 4)
+            res["whole_crops_over_decode_all"] = round(med("whole_crops") / med("decode_all"), 4)
+            print(json.dumps(res), flush=True)
+            del d_stream
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=200)
@@ -501,6 +627,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--tight", action="store_true")
     ap.add_argument("--direct", action="store_true")
+    ap.add_argument("--crop", action="store_true")
     ap.add_argument("--against", default=None,
                     help="with --tight or --direct: a second liblz4jpeg.so to alternate with")
     args = ap.parse_args()
@@ -509,6 +636,13 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("jpeg_pack_bench: needs a GPU (there is no CPU path to time)")
     dev = torch.device("cuda:0")
+    if args.crop:
+        if not args.once:                   # clock pre-warm (bench.py run_lz4)
+            d_warm = torch.zeros(256 << 20, dtype=torch.uint8, device=dev)
+            settle(lambda: d_warm.add_(1), torch.cuda.synchronize, ms=100.0, chunk=16)
+            del d_warm
+        crop_side(args, torch, jpeg, synth, dev)
+        return
     nt = jpeg.tiles(W, H)
     images = {}
     d_img = torch.empty(W * H * 4, dtype=torch.uint8, device=dev)

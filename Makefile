@@ -39,9 +39,11 @@ HDRS    := include/lz4r.h include/jpegr.h include/lz4jpeg_compat.h include/lz4jp
            $(CSRC)/lz4r_tiles.h $(CSRC)/lz4r_matches.h $(CSRC)/lz4r_scan.h $(CSRC)/lz4r_emit.h \
            $(CSRC)/lz4r_dec_layout.h $(CSRC)/lz4r_dec_parse.h $(CSRC)/lz4r_dec_blocks.h \
            $(CSRC)/lz4r_dec_bare.h $(CSRC)/lz4r_dec_read.h $(CSRC)/jpegr_pack_common.h \
-           $(CSRC)/jpegr_entropy_common.h $(CSRC)/jpegr_decode_common.h $(CSRC)/jpegr_crop.h
+           $(CSRC)/jpegr_entropy_common.h $(CSRC)/jpegr_decode_common.h $(CSRC)/jpegr_crop.h \
+           $(CSRC)/jpegr_pixel.h
 OBJS    := $(B)/lz4r.o $(B)/lz4r_gpudec.o $(B)/lz4r_read.o $(B)/jpegr.o $(B)/jpegr_blocks.o \
            $(B)/jpegr_entropy.o $(B)/jpegr_pack.o $(B)/jpegr_stream.o $(B)/jpegr_stream_enc.o \
+           $(B)/jpegr_thumb.o \
            $(B)/synth.o $(B)/synth_dev.o \
            $(B)/lz4r_decode.o $(B)/compat.o $(B)/compat_lz4.o
 
@@ -71,6 +73,16 @@ $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 
 chunk12: $(CHUNK12_LIB)
+
+# A/B only, not part of `all`: jpegr_thumb.hip (self-contained) with the other
+# form of its record read, for tools/jpeg_pack_bench.py --thumb --against
+# (DESIGN 4.14).  The product reads through the LDS window; this one does not.
+THUMB_ALT_LIB := $(B)/libjpegr_thumb_alt.so
+thumb-alt: $(THUMB_ALT_LIB)
+
+$(THUMB_ALT_LIB): $(CSRC)/jpegr_thumb.hip $(HDRS)
+	@mkdir -p $(B)
+	$(HIPCC) $(HIPFLAGS) -DJPRS_THUMB_WINDOW=0 -shared -o $@ $<
 
 $(CHUNK12_LIB): $(CSRC)/lz4r.hip $(HDRS)
 	@mkdir -p $(B)
@@ -146,7 +158,7 @@ clean:
 	rm -rf $(B) $(BIN) $(LIB) build
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib bin oracle tools chunk12 sanitize clean
+.PHONY: all lib bin oracle tools chunk12 thumb-alt sanitize clean
 
 # `make -s print-HIPFLAGS`: a variable's value (tests/test_isa.py builds with the product flags)
 print-%:

@@ -395,6 +395,65 @@ int jpegr_crop_device(const void *d_in, size_t in_len, int w, int h, int nimg,
                       int max_w, int max_h, void *d_out, size_t out_cap,
                       void *d_scratch, void *d_result, void *stream);
 
+/* Thumbnails: images [image0, image0 + nimage) of a JPR1 or JPT1 stream at 1/8
+ * scale, one RGBA8 pixel per tile, from the tiles' DC terms alone.  With
+ * gw = ceil(w / 8) and gh = ceil(h / 8), pixel (tx, ty) of an image's
+ * gw x gh thumbnail is pixel (8 tx, 8 ty) of what jpegr_reconstruct_device
+ * (d_rgba_orig = NULL) gives for that image's coefficients with every AC term
+ * set to 0 (alpha 255).  Such a tile reconstructs to one colour, so any of its
+ * pixels would do; an edge tile's DC carries the encoder's zero padding, and
+ * that is not corrected.  Tiles are in raster order and images in sequence:
+ * the output is nimage * gw * gh consecutive pixels, pixel k that of tile
+ * image0 * gw * gh + k of the stream.
+ * d_rgba_out (16-B aligned, or NULL): those pixels.  d_dc_out (8-B aligned,
+ * or NULL): per tile four int16 {Y, Cr, Cb, 0}, the three DC terms before any
+ * arithmetic -- zz[0] of each stream: the value of its first (count, value)
+ * RLE pair whose count is >= 1, else 0.  At least one of the two is given.
+ * The walk of a stream stops as soon as it has the DC and does not validate
+ * the rest of it:
+ *   - if jpegr_stream_decode_device accepts all three streams of a tile, the
+ *     tile's pixel and DC terms are exact;
+ *   - a tile whose record fails the record rules, and every tile when the
+ *     header or index is wrong, gets the colour of all-zero coefficients and
+ *     DC terms of 0, as decode + reconstruct gives;
+ *   - a stream that the full decoder rejects past its DC may still yield a DC
+ *     here: that tile's pixel and DC terms are unspecified.
+ * d_tile_offsets NULL: the call scans the index itself (d_scratch:
+ * jpegr_thumb_scratch_bytes(tiles of the whole stream) =
+ * jpegr_pack_scratch_bytes, 16-B aligned, required).  d_tile_offsets given
+ * (jpegr_stream_index_device's ntiles + 1 u64, 8-B aligned): no sizes or scan
+ * launch, d_scratch may be NULL.  The offsets are caller memory and not
+ * trusted: a tile whose offsets are not off[t] <= off[t + 1] <= in_len with a
+ * size of 12 .. 1,036 B is malformed, and the record rules apply inside that
+ * size.
+ * d_result: three u64 (8-B aligned), initialised by the call's own first
+ * launch -- no memset, no tag, no spin:
+ *   [0] the length the header and index imply, or off[ntiles] with offsets
+ *   [1] ~0 when consistent; 0 on a wrong header, dimensions or implied length;
+ *       else 1 + t for the first malformed tile t of the range (t counts from
+ *       the stream's first tile)
+ *   [2] the streams rejected inside the prefix examined (no codes, no RLE ints
+ *       or more than the plane holds, a code length of 0 or past 32, no code
+ *       at the bit position or only one that runs past nbits): a diagnostic,
+ *       at most jpegr_stream_decode_device's count; this call's, never
+ *       accumulated.  Such a stream's DC is 0.
+ * Asynchronous on `stream`, no host read-back, nothing kept on the host
+ * (capturable); several calls may be in flight at once, each with its own
+ * scratch and result.  JPEGR_ERR_ARG before any HIP call: NULL d_in or
+ * d_result, or both outputs NULL; bad dimensions or more than 2^32 tiles;
+ * nimage == 0 or image0 + nimage > nimg; in_len < 16; d_rgba_out or d_scratch
+ * not 16-B aligned, d_dc_out, d_tile_offsets or d_result not 8-B aligned; NULL
+ * d_scratch together with NULL d_tile_offsets.
+ * Whatever the stream and the offsets say, no read leaves d_in[0, in_len) and
+ * d_tile_offsets[0, ntiles], and no write leaves the two outputs' nimage *
+ * gw * gh * 4 and * 8 bytes, the scratch and the result words; table entries
+ * and bit bytes are read inside the checked record only. */
+size_t jpegr_thumb_scratch_bytes(size_t ntiles);
+int jpegr_thumb_device(const void *d_in, size_t in_len, int w, int h, int nimg,
+                       const void *d_tile_offsets, size_t image0, size_t nimage,
+                       void *d_rgba_out, void *d_dc_out, void *d_scratch, void *d_result,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

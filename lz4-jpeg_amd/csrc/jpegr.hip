@@ -25,6 +25,7 @@
 
 #include "jpeg_tables.h"
 #include "jpegr_crop.h"
+#include "jpegr_pixel.h"
 #include "../../include/jpegr.h"
 
 #pragma clang fp contract(off)
@@ -60,10 +61,6 @@ __constant__ int dZZ4inv[32];
 __constant__ int dRZn[128];
 __constant__ double dRZq[128];
 __constant__ double dRZa[128];
-
-__device__ __forceinline__ int clamp_u8(int v) {       // JPEG.c:132-139
-  return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
 
 // One pixel's contribution to the tile planes (JPEG.c:127, 157, 180;
 // chroma only from odd columns: chroma_subsample JPEG.c:329-331 +
@@ -312,29 +309,6 @@ __global__ __launch_bounds__(kEThreads) void jpeg_strip_kernel(
             *reinterpret_cast<const uint4 *>(reinterpret_cast<const uint8_t *>(olds) + off);
     }
   }
-}
-
-// (int)round(x) clamped to 0..255 (JPEG.c:440-446).  round() is half away
-// from zero; for x >= 0 that is trunc(x) + (x - trunc(x) >= 0.5), the
-// fraction exact in fp64.  A negative x clamps to 0 either way (trunc
-// toward zero gives <= 0 there), as does anything at or past 255.5.
-// Pinned by tests/test_gpu_jpeg_exact.py on samples an ulp either side of
-// k + 0.5 and past both clamps.
-__device__ __forceinline__ int round_clamp_u8(double x) {
-  const int i = (int)x;                          // v_cvt_i32_f64: toward zero, saturating
-  const int v = i + ((x - (double)i) >= 0.5 ? 1 : 0);
-  return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
-
-// The colour terms of assemble_image (JPEG.c:601-603): (int)(k * (double)d)
-// for d = Cr - 128 or Cb - 128 in -128..127 and k in {1.402, 0.344136,
-// 0.714136, 1.772}.  k d is never within 0.00104 of a nonzero integer on that
-// range (k = m / 10^e with d m not a multiple of 10^e unless d = 0), and the
-// fp64 product is within 1e-13 of k d, so its truncation is trunc(k d); the
-// fp32 product of the rounded k is within 3e-5 of k d, so it truncates the
-// same way.  Checked for all 4 x 256 cases by tests/test_tables.py.
-__device__ __forceinline__ int colour_term(float k, int d) {
-  return (int)(k * (float)d);
 }
 
 // ---- reconstruction: the decode side of the reference's main --------------

@@ -1,7 +1,8 @@
 // jpegr_pack_common.h -- the JPR stream's format (include/jpegr.h), once, for
 // every reader and writer of it: the record bounds and the slots' fields, the
 // stream header word and the JPT1 table coding, the index and the 16-B header
-// (written and read), the rule that makes a record malformed, the writers' run
+// (written and read), the readers' sizes launch (jprs_sizes), the rule that
+// makes a record malformed, the writers' run
 // of 16 tiles and its LDS image's way out to the stream, the scratch layout of
 // jpegr_pack_scratch_bytes, the index scan (lz4r_scan.h as it is) and a
 // workgroup's finish of that scan.  All of it is inlined into its callers; what
@@ -90,6 +91,25 @@ __device__ __forceinline__ bool header_ok(const uint8_t *in, uint64_t in_len, si
   for (uint32_t i = 0; ok && i < (uint32_t)kHdr; ++i)
     ok = in[i] == (uint8_t)(want[i >> 2] >> (8 * (i & 3))) || (accept_tight && i == 2 && in[i] == 'T');
   return ok;
+}
+
+// The first launch of a call that reads a stream by its own index (the direct
+// decode, the index call, the thumbnails): index -> u32 sizes, the scan's input,
+// and the header verdict in result[1].  kThird: the call's result has a third
+// word, cleared here (the index call has two words).
+template <bool kThird>
+__global__ __launch_bounds__(256) void jprs_sizes(const uint8_t *__restrict__ in, uint64_t in_len,
+                                                  size_t ntiles, size_t t_base, uint32_t w,
+                                                  uint32_t h, uint32_t nimg,
+                                                  uint32_t *__restrict__ tsz,
+                                                  uint64_t *__restrict__ result) {
+  const size_t t = t_base + (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= ntiles) return;
+  tsz[t] = get_index(in, in_len, t);
+  if (t == 0) {
+    result[1] = header_ok(in, in_len, ntiles, w, h, nimg, true) ? ~0ull : 0ull;
+    if constexpr (kThird) result[2] = 0ull;
+  }
 }
 
 // ---- the record rule ----------------------------------------------------------

@@ -6,7 +6,8 @@
 // rule that makes a record malformed are the ones unpack uses
 // (jpegr_pack_common.h: get_index, header_ok, record_rule).
 //
-//   jprs_sizes    index -> u32 sizes (the scan's input), the header verdict in
+//   jprs_sizes    (jpegr_pack_common.h: the thumbnails launch it too)
+//                 index -> u32 sizes (the scan's input), the header verdict in
 //                 result[1], result[2] = 0: the call's first launch initialises
 //                 its own result words, the later launches follow it in stream
 //                 order -- no memset, no tag, no spin
@@ -45,23 +46,6 @@
 #include "jpegr_pack_common.h"
 
 namespace {
-
-// kThird: the call's result has a third word (the direct decode's count of
-// rejected streams; the index call has two words)
-template <bool kThird>
-__global__ __launch_bounds__(256) void jprs_sizes(const uint8_t *__restrict__ in, uint64_t in_len,
-                                                  size_t ntiles, size_t t_base, uint32_t w,
-                                                  uint32_t h, uint32_t nimg,
-                                                  uint32_t *__restrict__ tsz,
-                                                  uint64_t *__restrict__ result) {
-  const size_t t = t_base + (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= ntiles) return;
-  tsz[t] = get_index(in, in_len, t);
-  if (t == 0) {
-    result[1] = header_ok(in, in_len, ntiles, w, h, nimg, true) ? ~0ull : 0ull;
-    if constexpr (kThird) result[2] = 0ull;
-  }
-}
 
 // A stream's bytes in the JPR stream: sp[0..4) its header, then its table
 // (StreamSrc below), then nby bit bytes at pb.  The record was checked, so all

@@ -2,7 +2,7 @@
  * JPEG_dec -- one image of a JPR1 or JPT1 stream (include/jpegr.h; JPEG_seq's
  * coefficients.jpr, or jpegr_pack_tight_device's output) back to pixels:
  *
- *   JPEG_dec <in.jpr> <out.png> [image [x y w h]]
+ *   JPEG_dec <in.jpr> <out.png> [image [x y w h | thumb]]
  *
  * The dimensions come from the stream's header (jpegr_stream_format); image
  * `image` (default 0) is the tile range [image * tiles, (image + 1) * tiles)
@@ -13,7 +13,10 @@
  * as a w x h PNG, decoded from the tiles they touch and nothing else
  * (jpegr_stream_index_device + jpegr_crop_device); a rectangle outside the
  * image, a zero-sized one or a bad verdict of either call is an error like the
- * others.  Prints nothing on stdout.  Any error -- an unreadable file, a bad header, an
+ * others.  With the literal word `thumb` after the image, that image's 1/8-scale
+ * thumbnail is written instead, ceil(w / 8) x ceil(h / 8) pixels, one per tile,
+ * from the tiles' DC terms alone (jpegr_thumb_device: no coefficients, no
+ * IDCT).  Prints nothing on stdout.  Any error -- an unreadable file, a bad header, an
  * image index out of range, an inconsistent stream (verdict other than ~0) or a
  * rejected entropy stream -- is one line on stderr, exit status 1 and no
  * output file.
@@ -80,12 +83,41 @@ static void crop(const void *d_in, size_t flen, int w, int h, int nimg, size_t n
   free(rgba);
 }
 
+/* the image's thumbnail, a pixel a tile, through jpegr_thumb_device */
+static void thumb(const void *d_in, size_t flen, int w, int h, int nimg, size_t ntiles, long image,
+                  const char *path) {
+  const int gw = (w + 7) / 8, gh = (h + 7) / 8;
+  const size_t out_b = (size_t)gw * (size_t)gh * 4;
+  void *d_scr = NULL, *d_res = NULL, *d_px = NULL;
+  if (hipMalloc(&d_scr, jpegr_thumb_scratch_bytes(ntiles)) != hipSuccess ||
+      hipMalloc(&d_res, 24) != hipSuccess || hipMalloc(&d_px, out_b) != hipSuccess)
+    fail("device allocation failed");
+  if (jpegr_thumb_device(d_in, flen, w, h, nimg, NULL, (size_t)image, 1, d_px, NULL, d_scr, d_res,
+                         NULL) != JPEGR_OK)
+    fail("kernel launch");
+  uint64_t res[3];
+  if (hipMemcpy(res, d_res, 24, hipMemcpyDeviceToHost) != hipSuccess) fail("copy out");
+  if (res[1] != ~(uint64_t)0) fail("inconsistent stream (header, index or a tile record)");
+  if (res[2] != 0) fail("malformed entropy stream");
+  uint8_t *rgba = malloc(out_b);
+  if (!rgba) fail("out of memory");
+  if (hipMemcpy(rgba, d_px, out_b, hipMemcpyDeviceToHost) != hipSuccess) fail("copy out");
+  if (lzj_png_write(path, gw, gh, rgba) != 0) {
+    remove(path);
+    fail("cannot write the PNG");
+  }
+  (void)hipFree(d_scr); (void)hipFree(d_res); (void)hipFree(d_px);
+  free(rgba);
+}
+
 int main(int argc, char **argv) {
-  if (argc != 3 && argc != 4 && argc != 8)
-    fail("usage: JPEG_dec <in.jpr> <out.png> [image [x y w h]]");
+  const int want_thumb = argc == 5 && strcmp(argv[4], "thumb") == 0;
+  if (argc != 3 && argc != 4 && argc != 8 && !want_thumb)
+    fail("usage: JPEG_dec <in.jpr> <out.png> [image [x y w h | thumb]]");
   long image = 0, rect[4] = {0, 0, 0, 0};
   if (argc >= 4) image = number(argv[3], "image index is not a number >= 0");
-  for (int i = 4; i < argc; ++i) rect[i - 4] = number(argv[i], "x y w h are not numbers >= 0");
+  for (int i = 4; i < argc && !want_thumb; ++i)
+    rect[i - 4] = number(argv[i], "x y w h are not numbers >= 0");
   FILE *f = fopen(argv[1], "rb");
   if (!f) fail("cannot read the input file");
   if (fseek(f, 0, SEEK_END) != 0) fail("cannot read the input file");
@@ -106,11 +138,14 @@ int main(int argc, char **argv) {
   if (per == 0 || ntiles == 0) fail("not a JPR stream (bad header)");
   const size_t npx = (size_t)w * (size_t)h;
 
-  if (argc == 8) {
+  if (argc == 8 || want_thumb) {
     void *d_stream = NULL;
     if (hipMalloc(&d_stream, (size_t)flen) != hipSuccess) fail("device allocation failed");
     if (hipMemcpy(d_stream, data, (size_t)flen, hipMemcpyHostToDevice) != hipSuccess) fail("copy in");
-    crop(d_stream, (size_t)flen, w, h, nimg, ntiles, image, rect, argv[2]);
+    if (want_thumb)
+      thumb(d_stream, (size_t)flen, w, h, nimg, ntiles, image, argv[2]);
+    else
+      crop(d_stream, (size_t)flen, w, h, nimg, ntiles, image, rect, argv[2]);
     (void)hipFree(d_stream);
     free(data);
     return 0;

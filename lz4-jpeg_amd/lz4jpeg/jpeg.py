@@ -405,6 +405,83 @@ def crop_device(d_stream, in_len, w, h, nimg, d_offsets, d_image, d_x, d_y, d_w,
     return d_out, d_dst, n
 
 
+# -- thumbnails -----------------------------------------------------------------
+def thumb_device(d_stream, in_len, w, h, nimg, first=0, count=None, d_offsets=None, d_out=None,
+                 d_dc=None, want_dc=False, scratch=None, d_result=None, stream=None):
+    """Images [first, first + count) of a JPR1 or JPT1 stream's first in_len
+    bytes at 1/8 scale, one RGBA8 pixel per tile, from the DC terms alone
+    (jpegr_thumb_device; count None = up to the last image).  d_offsets:
+    stream_index_device's offsets, which spare the call its own index scan (and
+    its scratch); None: the call scans.  d_out: uint8, count * tiles(w, h) * 4
+    bytes (allocated when None); d_dc: int16, four per tile {Y, Cr, Cb, 0}, the
+    DC terms themselves (allocated when None and want_dc; else not written).
+    Returns (d_out, d_dc, d_result): d_result three int64 on the
+    device, [0] the implied length, [1] -1 (all ones) when consistent, 0 on a
+    wrong header or index, 1 + t for the first malformed tile t of the range,
+    [2] the streams rejected inside the prefix examined (jpegr.h).
+    Asynchronous: no read-back."""
+    import torch
+    if count is None:
+        count = nimg - first
+    if first < 0 or count <= 0 or first + count > nimg:
+        raise ValueError("image range outside the stream")
+    if in_len > d_stream.numel():
+        raise ValueError("in_len past the end of d_stream")
+    nt, n = nimg * tiles(w, h), count * tiles(w, h)
+    dev = d_stream.device
+    if d_offsets is not None and d_offsets.numel() < nt + 1:
+        raise ValueError("d_offsets smaller than ntiles + 1")
+    if d_dc is None and want_dc:
+        d_dc = torch.empty(n * 4, dtype=torch.int16, device=dev)
+    elif d_dc is not None and d_dc.numel() * d_dc.element_size() < n * 8:
+        raise ValueError("d_dc smaller than four int16 per tile")
+    if d_out is None:
+        d_out = torch.empty(n * 4, dtype=torch.uint8, device=dev)
+    elif d_out.numel() * d_out.element_size() < n * 4:
+        raise ValueError("d_out smaller than four bytes per tile")
+    if d_result is None:
+        d_result = torch.empty(3, dtype=torch.int64, device=dev)
+    if scratch is None and d_offsets is None:
+        scratch = _pack_scratch(nt, dev)
+    rc = _lib.lib().jpegr_thumb_device(
+        ctypes.c_void_p(d_stream.data_ptr()), in_len, w, h, nimg,
+        ctypes.c_void_p(d_offsets.data_ptr() if d_offsets is not None else 0), first, count,
+        ctypes.c_void_p(d_out.data_ptr()), ctypes.c_void_p(d_dc.data_ptr() if d_dc is not None else 0),
+        ctypes.c_void_p(scratch.data_ptr() if scratch is not None else 0),
+        ctypes.c_void_p(d_result.data_ptr()), _stream_handle(stream))
+    if rc != 0:
+        raise JpegError(rc, "jpegr_thumb_device")
+    return d_out, d_dc, d_result
+
+
+def _thumbnails(d_stream, w, h, nimg, first, count, d_offsets):
+    if count is None:
+        count = nimg - first
+    d_out, _, d_result = thumb_device(d_stream, d_stream.numel(), w, h, nimg, first, count,
+                                      d_offsets=d_offsets)
+    res = d_result.cpu().tolist()
+    if res[1] != -1:
+        raise JpegError(-1, f"thumbnails: inconsistent stream (verdict {res[1]})")
+    if res[2] != 0:
+        raise JpegError(-1, "thumbnails: malformed entropy stream")
+    return d_out.view(count, (h + 7) // 8, (w + 7) // 8, 4), w, h, count
+
+
+def thumbnails_device(d_stream, first=0, count=None):
+    """1/8-scale thumbnails of images [first, first + count) of a JPR1 or JPT1
+    stream (uint8 tensor, exactly the stream; count None = up to the last) ->
+    (uint8 tensor [count, ceil(h / 8), ceil(w / 8), 4], w, h, count): pixel
+    (tx, ty) is pixel (8 tx, 8 ty) of the image reconstructed from its DC terms
+    alone.  Reads the 16 header bytes back, then the result words; the other
+    images are not touched.  Raises JpegError on an inconsistent stream
+    (d_result[1] != ~0) or a stream rejected before its DC (d_result[2] != 0),
+    as decompress_images_device does."""
+    if d_stream.numel() < 16:
+        raise JpegError(-1, "thumbnails_device: shorter than a header")
+    w, h, nimg, _ = stream_format(d_stream[:16].cpu().numpy().tobytes())
+    return _thumbnails(d_stream, w, h, nimg, first, count, None)
+
+
 class StreamReader:
     """Random access into one JPR1 or JPT1 stream on the device (a uint8
     tensor, exactly the stream): the header is read back once and the index is
@@ -437,6 +514,11 @@ class StreamReader:
         """crop_device on this stream: (d_out, d_dst, delivered)."""
         return crop_device(self.d_stream, self.length, self.w, self.h, self.nimg, self.d_offsets,
                            d_image, d_x, d_y, d_w, d_h, max_w, max_h, **kw)
+
+    def thumbnails(self, first=0, count=None):
+        """thumbnails_device on this stream, through the kept offsets: (uint8
+        tensor [count, ceil(h / 8), ceil(w / 8), 4], w, h, count)."""
+        return _thumbnails(self.d_stream, self.w, self.h, self.nimg, first, count, self.d_offsets)
 
 
 def stream_encode_scratch_bytes(ntiles, cap):

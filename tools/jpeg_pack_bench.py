@@ -6,7 +6,7 @@ launches.
 
     python tools/jpeg_pack_bench.py [--steps K] [--once N]
                                     [--decode | --tight [--against LIB] | --direct [--against LIB]
-                                     | --crop]
+                                     | --crop | --thumb [--against LIB]]
 
 Images: bench.py's 3840x2160 random image (synth.rand_rgba_device, seed 1)
 and a 3840x2160 smooth one (tests/test_gpu_entropy.py's generator).  Prints
@@ -58,7 +58,24 @@ decode + reconstruct of the same images: the price of the crop mapping where
 it has nothing to save.  All in this run after the same pre-warm and settle,
 alternated over --rounds rounds, event-timed; the crops' bytes are checked
 against the gather's.  With --once N: N crop calls per stream and nothing
-else."""
+else.
+
+--thumb: 1/8-scale thumbnails from the DC terms alone (jpegr_thumb_device), for
+profiles/jpr_thumb_bench.md: --crop's streams (16 images of 1920x1080, random
+and smooth, JPR1 and JPT1) and four paths to the 16 thumbnails of 240x135:
+thumb_device with the offsets kept (the index built once outside the timed
+call), thumb_device scanning the index itself, the index call alone, and what a
+caller had to do before: the direct decode and reconstruction of all 16 images
+followed by torch.nn.functional.avg_pool2d(.., 8).  That baseline's pixels are
+not the thumbnail's -- a mean of 64 rounded samples, AC terms included, against
+the one sample of the DC-only tile -- so only the thumbnail paths' bytes are
+checked, against each other and against every eighth pixel of the
+reconstruction of the DC-only coefficients.  Reports each path's stream bytes
+per ms and its ratio to the baseline.  --against LIB adds the same two
+thumbnail calls of a second build of jpegr_thumb.hip (make thumb-alt: the other
+form of the record read) to the same rounds.  All in this run after the same
+pre-warm and settle, alternated over --rounds rounds, event-timed.  With
+--once N: N thumbnail calls (offsets kept) per stream and nothing else."""
 import argparse
 import json
 import os
@@ -619,6 +636,105 @@ def crop_side(args, torch, jpeg, synth, dev):
             del d_stream
 
 
+def thumb_side(args, torch, jpeg, synth, dev, other):
+    """Thumbnails straight from the stream beside decode-everything-and-pool."""
+    import ctypes
+    per = jpeg.tiles(CW, CH)
+    nt = CN * per
+    px = CW * CH
+    gw, gh = (CW + 7) // 8, (CH + 7) // 8
+    images = {}
+    d_img = torch.empty(CN * px * 4, dtype=torch.uint8, device=dev)
+    synth.rand_rgba_device(d_img, 0, CN * px, seed=1)
+    images["random"] = d_img
+    images["smooth"] = torch.from_numpy(smooth_image(CW, CH)).to(dev).reshape(-1).repeat(CN)
+    d_offs = torch.empty(nt + 1, dtype=torch.int64, device=dev)
+    d_ires = torch.empty(2, dtype=torch.int64, device=dev)
+    d_res, d_res_scan, d_res3, d_res_alt = (torch.empty(3, dtype=torch.int64, device=dev) for _ in range(4))
+    iscr = torch.empty(int(jpeg._lib.lib().jpegr_pack_scratch_bytes(nt)), dtype=torch.uint8, device=dev)
+    d_out, d_out_scan, d_out_alt = (torch.empty(nt * 4, dtype=torch.uint8, device=dev) for _ in range(3))
+    d_coef = torch.empty(nt * 128, dtype=torch.int16, device=dev)
+    vp = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+    if other is not None:
+        other.jpegr_thumb_device.restype = ctypes.c_int
+        other.jpegr_thumb_device.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
+                                             ctypes.c_size_t] + [ctypes.c_void_p] * 5
+    for name, img in images.items():
+        for tight in (False, True):
+            d_stream = jpeg.compress_device(img, CW, CH, CN, tight=tight)
+            n = d_stream.numel()
+
+            def index():
+                jpeg.stream_index_device(d_stream, n, CW, CH, CN, d_offsets=d_offs, d_result=d_ires,
+                                         scratch=iscr)
+
+            def thumbs():
+                jpeg.thumb_device(d_stream, n, CW, CH, CN, d_offsets=d_offs, d_out=d_out, d_result=d_res)
+
+            def thumbs_scan():
+                jpeg.thumb_device(d_stream, n, CW, CH, CN, d_out=d_out_scan, scratch=iscr,
+                                  d_result=d_res_scan)
+
+            def alt(offs):
+                rc = other.jpegr_thumb_device(vp(d_stream), n, CW, CH, CN, vp(d_offs if offs else None), 0,
+                                              CN, vp(d_out_alt), None, vp(iscr), vp(d_res_alt),
+                                              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+                assert rc == 0
+
+            def decode_all():
+                jpeg.decode_stream_device(d_stream, n, CW, CH, CN, d_coef=d_coef, d_result=d_res3,
+                                          scratch=iscr)
+                return jpeg.reconstruct_device(d_coef, CW, CH, CN)
+
+            def decode_all_and_pool():
+                full = decode_all().view(CN, CH, CW, 4).permute(0, 3, 1, 2).float()
+                return torch.nn.functional.avg_pool2d(full, 8)
+
+            index()
+            if args.once:
+                for _ in range(args.once):
+                    thumbs()
+                torch.cuda.synchronize()
+                continue
+            thumbs()
+            thumbs_scan()
+            decode_all()
+            dc_only = torch.zeros_like(d_coef).view(nt, 128)
+            dc_only[:, [0, 64, 96]] = d_coef.view(nt, 128)[:, [0, 64, 96]]
+            want = jpeg.reconstruct_device(dc_only.view(-1), CW, CH, CN).view(CN, CH, CW, 4)[:, ::8, ::8]
+            torch.cuda.synchronize()
+            ok = bool(torch.equal(d_out.view(CN, gh, gw, 4), want)) and bool(torch.equal(d_out, d_out_scan)) \
+                and d_ires.cpu().tolist() == [n, -1] and d_res.cpu().tolist() == [n, -1, 0] \
+                and d_res_scan.cpu().tolist() == [n, -1, 0] and d_res3.cpu().tolist() == [n, -1, 0]
+            calls = [("thumbs", thumbs), ("thumbs_scan", thumbs_scan), ("index", index),
+                     ("decode_all_and_pool", decode_all_and_pool), ("decode_all", decode_all)]
+            if other is not None:
+                calls += [("alt_thumbs", lambda: alt(True)), ("alt_thumbs_scan", lambda: alt(False))]
+                for offs in (True, False):
+                    alt(offs)
+                    torch.cuda.synchronize()
+                    ok = ok and bool(torch.equal(d_out_alt, d_out)) and d_res_alt.cpu().tolist() == [n, -1, 0]
+            del dc_only, want
+            res = {"stream": f"{name} {CN} x {CW}x{CH} {'JPT1' if tight else 'JPR1'}", "tiles": nt,
+                   "stream_bytes": n, "thumbnails": f"{CN} of {gw}x{gh}", "outputs_equal": ok,
+                   "steps": args.steps, "rounds": args.rounds}
+            ms = {k: [] for k, _ in calls}
+            for r in range(args.rounds):                  # alternated; the order turns with the round
+                for key, fn in calls[r % len(calls):] + calls[:r % len(calls)]:
+                    settle(fn, torch.cuda.synchronize, chunk=4)
+                    ms[key].append(timed(fn, args.steps, torch))
+            for key, _ in calls:
+                res[key + "_ms"] = spread(ms[key])
+            med = lambda k: res[k + "_ms"]["median"]
+            for key, _ in calls:
+                res[key + "_stream_MB_per_ms"] = round(n / 1e6 / med(key), 2)
+                if key != "decode_all_and_pool":
+                    res[key + "_over_decode_all_and_pool"] = round(med(key) / med("decode_all_and_pool"), 4)
+            print(json.dumps(res), flush=True)
+            del d_stream
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=200)
@@ -628,20 +744,28 @@ def main():
     ap.add_argument("--tight", action="store_true")
     ap.add_argument("--direct", action="store_true")
     ap.add_argument("--crop", action="store_true")
+    ap.add_argument("--thumb", action="store_true")
     ap.add_argument("--against", default=None,
-                    help="with --tight or --direct: a second liblz4jpeg.so to alternate with")
+                    help="with --tight or --direct: a second liblz4jpeg.so to alternate with; "
+                         "with --thumb: a second build of jpegr_thumb.hip (make thumb-alt)")
     args = ap.parse_args()
     import torch
     from lz4jpeg import jpeg, synth
     if not torch.cuda.is_available():
         sys.exit("jpeg_pack_bench: needs a GPU (there is no CPU path to time)")
     dev = torch.device("cuda:0")
-    if args.crop:
+    if args.crop or args.thumb:
         if not args.once:                   # clock pre-warm (bench.py run_lz4)
             d_warm = torch.zeros(256 << 20, dtype=torch.uint8, device=dev)
             settle(lambda: d_warm.add_(1), torch.cuda.synchronize, ms=100.0, chunk=16)
             del d_warm
-        crop_side(args, torch, jpeg, synth, dev)
+        if args.crop:
+            crop_side(args, torch, jpeg, synth, dev)
+        else:
+            import ctypes
+            thumb_side(args, torch, jpeg, synth, dev,
+                       ctypes.CDLL(os.path.abspath(args.against), mode=ctypes.RTLD_LOCAL)
+                       if args.against else None)
         return
     nt = jpeg.tiles(W, H)
     images = {}

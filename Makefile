@@ -5,6 +5,7 @@
 #   lz4-jpeg_amd/bin/LZ4_seq, JPEG_seq    drop-in executables (file contract),
 #                                         also as LZ4_seq.exe / JPEG_seq.exe
 #   lz4-jpeg_amd/bin/JPEG_dec             coefficients.jpr -> PNG (also JPEG_dec.exe)
+#   lz4-jpeg_amd/bin/JPEG_sel             images or tile windows of a .jpr -> a new .jpr (also JPEG_sel.exe)
 #   oracle/liboracle.so (+ oracle/_ref)   test-only CPU checker
 #   lz4-jpeg_amd/build/liblz4r_chunk12.so test-only: the compressor alone, cut into
 #                                         launch chunks of 2^12 blocks
@@ -43,7 +44,7 @@ HDRS    := include/lz4r.h include/jpegr.h include/lz4jpeg_compat.h include/lz4jp
            $(CSRC)/jpegr_pixel.h
 OBJS    := $(B)/lz4r.o $(B)/lz4r_gpudec.o $(B)/lz4r_read.o $(B)/jpegr.o $(B)/jpegr_blocks.o \
            $(B)/jpegr_entropy.o $(B)/jpegr_pack.o $(B)/jpegr_stream.o $(B)/jpegr_stream_enc.o \
-           $(B)/jpegr_thumb.o \
+           $(B)/jpegr_thumb.o $(B)/jpegr_select.o \
            $(B)/synth.o $(B)/synth_dev.o \
            $(B)/lz4r_decode.o $(B)/compat.o $(B)/compat_lz4.o
 
@@ -53,7 +54,7 @@ lib: $(LIB)
 
 bin: $(BIN)/LZ4_seq $(BIN)/JPEG_seq $(BIN)/LZ4_seq.exe $(BIN)/JPEG_seq.exe \
      $(BIN)/LZ4_par $(BIN)/JPEG_par $(BIN)/LZ4_par.exe $(BIN)/JPEG_par.exe \
-     $(BIN)/JPEG_dec $(BIN)/JPEG_dec.exe
+     $(BIN)/JPEG_dec $(BIN)/JPEG_dec.exe $(BIN)/JPEG_sel $(BIN)/JPEG_sel.exe
 
 $(CSRC)/jpeg_tables.h: $(CSRC)/gen_jpeg_tables.py
 	python3 $< > $@
@@ -100,6 +101,10 @@ $(BIN)/JPEG_seq: $(B)/jpeg_seq.o $(B)/png_io.o $(OBJS)
 $(BIN)/JPEG_dec: $(B)/jpeg_dec.o $(B)/png_io.o $(OBJS)
 	@mkdir -p $(BIN)
 	$(HIPCC) --offload-arch=$(ARCH) -o $@ $^ -lz
+
+$(BIN)/JPEG_sel: $(B)/jpeg_sel.o $(OBJS)
+	@mkdir -p $(BIN)
+	$(HIPCC) --offload-arch=$(ARCH) -o $@ $^
 
 # the parallel drivers' executables (Experiment/*_parallel_experiment.c)
 $(B)/lz4_par.o: $(HOST)/lz4_seq.c $(HDRS)

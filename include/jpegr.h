@@ -454,6 +454,77 @@ int jpegr_thumb_device(const void *d_in, size_t in_len, int w, int h, int nimg,
                        void *d_rgba_out, void *d_dc_out, void *d_scratch, void *d_result,
                        void *stream);
 
+/* Editing a stream without decoding it: a new JPR1 or JPT1 stream made of
+ * tiles of an existing one.  A tile record is self-contained and a record's
+ * place is the scan of the index, so a subset of a stream is a gather of
+ * records behind a new index and header, and the other format is the same
+ * records with each stream's table written the other way; no Huffman walk, no
+ * IDCT, and the result is exact by construction.
+ *
+ * jpegr_select_device: the output is one well-formed stream of nitems images
+ * of out_w x out_h.  Image k of it is the tile grid ceil(out_w / 8) x
+ * ceil(out_h / 8) of source image items[k].image that starts at tile column
+ * x / 8 and tile row y / 8, in raster order; whole images are x = y = 0,
+ * out_w = w, out_h = h.  Items may repeat and come in any order.  The tiles
+ * are the source's as they are: a window whose out_w is not a multiple of 8
+ * and that ends inside the image keeps its last tile column whole, where an
+ * encode of the cropped pixels would have padded it with zeros (and so for
+ * out_h).  The header is the format's magic, out_w, out_h, nitems.
+ * The target format is `format`, or the source's when format is 0 (JPR1 when
+ * the source has no valid header).
+ *   target == the source's   records are copied verbatim, non-canonical JPT1
+ *                            modes included; only their offsets and size are
+ *                            checked
+ *   JPR1 -> JPT1             every stream's table in the writers' canonical mode:
+ *                            the bytes jpegr_pack_tight_device writes
+ *   JPT1 -> JPR1             modes 1 and 2 expanded to 3-B entries
+ * In both re-codings the bit bytes and the rle_len, ncodes and nbits fields are
+ * copied and the record rules are applied to the source record.
+ * An item is bad when image >= nimg; x or y is not a multiple of 8;
+ * x + out_w > w or y + out_h > h (no sum wraps); or the source's 16 header
+ * bytes are not a JPR1 or JPT1 header for w, h, nimg (every item is bad then).
+ * Every tile of a bad item is written as the empty record: 12 zero bytes, three
+ * streams with ncodes = 0, which every reader turns into zero coefficients.  A
+ * tile of a good item becomes the empty record too when its offsets are not
+ * off[t] <= off[t + 1] <= in_len with a size of 12 .. 1,036 B (the offsets are
+ * caller memory and not trusted, as for jpegr_crop_device) or, when re-coding,
+ * the record rules reject the record.  Every other tile is exact, whatever the
+ * bad ones do.
+ * d_result: three u64 (8-B aligned), initialised by the call's own first launch
+ * -- no memset, no tag, no spin:
+ *   [0] the length, or the capacity needed
+ *   [1] ~0, or 1 + the index of the first bad item
+ *   [2] the tiles of good items written as the empty record: this call's count,
+ *       never accumulated
+ * The rest is jpegr_pack_device's contract: a u64 at d_out_len (8-B aligned)
+ * holds the length, or the exact capacity needed when that exceeds cap, in
+ * which case d_out[0, cap) holds the stream's first cap bytes and nothing at or
+ * past cap is written.  d_out 16-B aligned; d_in any alignment; d_items,
+ * d_tile_offsets (jpegr_stream_index_device's ntiles + 1 u64) and d_result
+ * 8-B aligned; d_scratch 16-B aligned, jpegr_select_scratch_bytes(nitems,
+ * out_w, out_h) bytes (0 on a bad argument).  Asynchronous on `stream`, no host
+ * read-back, nothing kept on the host (capturable, replayable); several calls
+ * may be in flight at once, each with its own scratch and result.  No read
+ * leaves d_in[0, in_len), d_tile_offsets[0, ntiles] and d_items[0, nitems),
+ * whatever they say and wherever d_in lies: a record is read as the aligned
+ * dwords that lie wholly inside it and its other bytes one by one.
+ * JPEGR_ERR_ARG before any HIP call: a NULL pointer; bad source dimensions or
+ * more than 2^32 source tiles; nitems == 0 or past 2^31 - 1 (the header's
+ * count); out_w or out_h <= 0, out_w > w, out_h > h; more than 2^32 output
+ * tiles; a format other than 0, JPEGR_STREAM_JPR1 and JPEGR_STREAM_JPT1;
+ * in_len < 16; a misalignment listed above.
+ *
+ * Joining streams of one w, h and format needs no call: a new header with the
+ * sum of the image counts, the indexes back to back, then the records back to
+ * back (INTEGRATION.md has the copies). */
+typedef struct jpegr_sel { uint64_t image, x, y; } jpegr_sel;
+
+size_t jpegr_select_scratch_bytes(size_t nitems, int out_w, int out_h);
+int jpegr_select_device(const void *d_in, size_t in_len, int w, int h, int nimg,
+                        const void *d_tile_offsets, const void *d_items, size_t nitems,
+                        int out_w, int out_h, int format, void *d_out, size_t cap,
+                        void *d_out_len, void *d_scratch, void *d_result, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -77,6 +77,9 @@ SIGNATURES = [
     ("jpegr_thumb_scratch_bytes", _c_size, [_c_size]),
     ("jpegr_thumb_device", _i, [_vp, _c_size, _i, _i, _i, _vp, _c_size, _c_size, _vp, _vp, _vp, _vp,
                                 _vp]),
+    ("jpegr_select_scratch_bytes", _c_size, [_c_size, _i, _i]),
+    ("jpegr_select_device", _i, [_vp, _c_size, _i, _i, _i, _vp, _vp, _c_size, _i, _i, _i, _vp, _c_size,
+                                 _vp, _vp, _vp, _vp]),
     ("jpegr_planes_device", _i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     ("jpegr_dct_blocks_device", _i, [_vp, _i, _i, _i, _vp, _vp]),
     ("jpegr_quantize_device", _i, [_vp, _vp, _i, _c_size, _vp]),

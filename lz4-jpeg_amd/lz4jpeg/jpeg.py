@@ -482,6 +482,106 @@ def thumbnails_device(d_stream, first=0, count=None):
     return _thumbnails(d_stream, w, h, nimg, first, count, None)
 
 
+# -- editing a stream without decoding it ------------------------------------------
+def select_scratch_bytes(nitems, out_w, out_h):
+    return int(_lib.lib().jpegr_select_scratch_bytes(nitems, out_w, out_h))
+
+
+def _format_arg(tight):
+    return 0 if tight is None else STREAM_JPT1 if tight else STREAM_JPR1
+
+
+def select_device(d_stream, in_len, w, h, nimg, d_offsets, d_image, d_x, d_y, out_w, out_h, tight=None,
+                  d_out=None, d_len=None, scratch=None, d_result=None, stream=None, cap=None):
+    """A new stream of d_image.numel() images of out_w x out_h from tiles of
+    a JPR1 or JPT1 stream's first in_len bytes, nothing decoded
+    (jpegr_select_device): image k is the tile grid of source image d_image[k]
+    that starts at pixel (d_x[k], d_y[k]), both multiples of 8.  d_image, d_x,
+    d_y: int64 tensors on the device; d_offsets: stream_index_device's.
+    tight: None keeps the source's format, False writes JPR1, True JPT1.
+    Returns (d_out, d_len, d_result): d_out a uint8 tensor (pack_bound(out_w,
+    out_h, nitems) bytes when not given), d_len one int64 holding the stream
+    length -- or the capacity needed when that exceeds d_out's size (or `cap`,
+    a smaller capacity to write within), in which case nothing past it is
+    written -- and d_result three int64, [0] the
+    length again, [1] -1 (all ones) or 1 + the first bad item, [2] the tiles
+    of good items written as the empty record (jpegr.h).  Asynchronous: no
+    read-back."""
+    import torch
+    nitems = d_image.numel()
+    if nitems == 0 or d_x.numel() != nitems or d_y.numel() != nitems:
+        raise ValueError("d_image, d_x and d_y hold one entry per item, and at least one")
+    if in_len > d_stream.numel():
+        raise ValueError("in_len past the end of d_stream")
+    if d_offsets.numel() < nimg * tiles(w, h) + 1:
+        raise ValueError("d_offsets smaller than ntiles + 1")
+    dev = d_stream.device
+    d_items = torch.stack((d_image, d_x, d_y), dim=1).contiguous()
+    if d_out is None:
+        d_out = torch.empty(pack_bound(out_w, out_h, nitems), dtype=torch.uint8, device=dev)
+    if cap is None:
+        cap = d_out.numel()
+    elif cap > d_out.numel():
+        raise ValueError("cap past the end of d_out")
+    if d_len is None:
+        d_len = torch.zeros(1, dtype=torch.int64, device=dev)
+    if d_result is None:
+        d_result = torch.empty(3, dtype=torch.int64, device=dev)
+    need = select_scratch_bytes(nitems, out_w, out_h)
+    if scratch is None:
+        scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    elif scratch.numel() < need:
+        raise ValueError("scratch smaller than select_scratch_bytes(nitems, out_w, out_h)")
+    rc = _lib.lib().jpegr_select_device(
+        ctypes.c_void_p(d_stream.data_ptr()), in_len, w, h, nimg,
+        ctypes.c_void_p(d_offsets.data_ptr()), ctypes.c_void_p(d_items.data_ptr()), nitems, out_w, out_h,
+        _format_arg(tight), ctypes.c_void_p(d_out.data_ptr()), cap,
+        ctypes.c_void_p(d_len.data_ptr()), ctypes.c_void_p(scratch.data_ptr()),
+        ctypes.c_void_p(d_result.data_ptr()), _stream_handle(stream))
+    if rc != 0:
+        raise JpegError(rc, "jpegr_select_device")
+    return d_out, d_len, d_result
+
+
+def concat_streams(streams):
+    """Streams (uint8 device tensors, each exactly a stream) of one w, h and
+    format joined into one: a new header with the sum of the image counts, the
+    indexes back to back, then the records back to back, by device copies.
+    Reads each 16-B header back.  Raises JpegError when w, h or the format
+    differ or a stream is shorter than its header and index."""
+    import torch
+    streams = list(streams)
+    if not streams:
+        raise ValueError("no streams")
+    heads = []
+    for d in streams:
+        if d.numel() < 16:
+            raise JpegError(-1, "concat_streams: shorter than a header")
+        heads.append(stream_format(d[:16].cpu().numpy().tobytes()))
+    w, h, _, tight = heads[0]
+    if any((hw, hh, ht) != (w, h, tight) for hw, hh, _, ht in heads):
+        raise JpegError(-1, "concat_streams: the streams differ in w, h or format")
+    nts = [n * tiles(w, h) for _, _, n, _ in heads]
+    if any(d.numel() < 16 + 2 * nt for d, nt in zip(streams, nts)):
+        raise JpegError(-1, "concat_streams: shorter than its index")
+    nimg = sum(n for _, _, n, _ in heads)
+    if nimg > 0x7FFFFFFF:
+        raise JpegError(-1, "concat_streams: too many images")
+    total = 16 + sum(d.numel() - 16 for d in streams)
+    out = torch.empty(total, dtype=torch.uint8, device=streams[0].device)
+    head = (b"JPT1" if tight else b"JPR1") + b"".join(int(v).to_bytes(4, "little") for v in (w, h, nimg))
+    out[:16].copy_(torch.frombuffer(bytearray(head), dtype=torch.uint8))
+    pos = 16
+    for d, nt in zip(streams, nts):
+        out[pos:pos + 2 * nt].copy_(d[16:16 + 2 * nt])
+        pos += 2 * nt
+    for d, nt in zip(streams, nts):
+        n = d.numel() - 16 - 2 * nt
+        out[pos:pos + n].copy_(d[16 + 2 * nt:])
+        pos += n
+    return out
+
+
 class StreamReader:
     """Random access into one JPR1 or JPT1 stream on the device (a uint8
     tensor, exactly the stream): the header is read back once and the index is
@@ -519,6 +619,54 @@ class StreamReader:
         """thumbnails_device on this stream, through the kept offsets: (uint8
         tensor [count, ceil(h / 8), ceil(w / 8), 4], w, h, count)."""
         return _thumbnails(self.d_stream, self.w, self.h, self.nimg, first, count, self.d_offsets)
+
+    def select(self, images=None, x=0, y=0, w=None, h=None, tight=None):
+        """A uint8 tensor of exactly the new stream whose image k is the w x h
+        tile window of image images[k] at pixel (x, y) -- ints, or one per
+        item; both multiples of 8 -- with nothing decoded (select_device).
+        images None: every image in order; w, h None: the source's; tight
+        None: the source's format, False JPR1, True JPT1.  Reads the length
+        back once and runs once more at the needed capacity when the first
+        guess was short.  Raises JpegError on a bad item (d_result[1] != ~0)
+        or a tile written as the empty record (d_result[2] != 0)."""
+        import torch
+        dev = self.d_stream.device
+        images = list(range(self.nimg)) if images is None else [int(i) for i in images]
+        n = len(images)
+        if n == 0:
+            raise ValueError("no images selected")
+        w = self.w if w is None else w
+        h = self.h if h is None else h
+        if not (0 < w <= self.w and 0 < h <= self.h):
+            raise ValueError("the window is larger than the image, or empty")
+
+        def col(v):
+            v = [int(a) for a in v] if hasattr(v, "__iter__") else [int(v)] * n
+            if len(v) != n:
+                raise ValueError("x and y hold one entry per item")
+            return torch.tensor(v, dtype=torch.int64, device=dev)
+
+        cols = (torch.tensor(images, dtype=torch.int64, device=dev), col(x), col(y))
+        nt_out, nt_in = n * tiles(w, h), self.nimg * tiles(self.w, self.h)
+        # the source's mean record (a quarter more: JPR1 from JPT1 grows), never past the bound
+        cap = min(pack_bound(w, h, n), 16 + 2 * nt_out + 1024 + (5 * self.length * nt_out) // (4 * nt_in))
+        for _ in range(2):
+            d_out = torch.empty(cap, dtype=torch.uint8, device=dev)
+            _, _, d_result = select_device(self.d_stream, self.length, self.w, self.h, self.nimg,
+                                           self.d_offsets, *cols, w, h, tight=tight, d_out=d_out)
+            need, bad, empty = (int(v) for v in d_result.cpu().tolist())
+            if bad != -1:
+                raise JpegError(-1, f"jpegr_select_device: item {bad - 1}")
+            if empty != 0:
+                raise JpegError(-1, f"jpegr_select_device: {empty} malformed tile records")
+            if need <= cap:
+                return d_out[:need].clone()
+            cap = need
+        raise JpegError(-1, "jpegr_select_device: the needed capacity changed between two calls")
+
+    def transcode(self, tight):
+        """The whole stream in the other (or the same) format: select of everything."""
+        return self.select(tight=tight)
 
 
 def stream_encode_scratch_bytes(ntiles, cap):

@@ -6,7 +6,7 @@ launches.
 
     python tools/jpeg_pack_bench.py [--steps K] [--once N]
                                     [--decode | --tight [--against LIB] | --direct [--against LIB]
-                                     | --crop | --thumb [--against LIB]]
+                                     | --crop | --thumb [--against LIB] | --select]
 
 Images: bench.py's 3840x2160 random image (synth.rand_rgba_device, seed 1)
 and a 3840x2160 smooth one (tests/test_gpu_entropy.py's generator).  Prints
@@ -75,7 +75,21 @@ per ms and its ratio to the baseline.  --against LIB adds the same two
 thumbnail calls of a second build of jpegr_thumb.hip (make thumb-alt: the other
 form of the record read) to the same rounds.  All in this run after the same
 pre-warm and settle, alternated over --rounds rounds, event-timed.  With
---once N: N thumbnail calls (offsets kept) per stream and nothing else."""
+--once N: N thumbnail calls (offsets kept) per stream and nothing else.
+
+--select: editing a stream without decoding it (jpegr_select_device), for
+profiles/jpr_select_bench.md: --crop's streams and three edits of each -- 8 of
+the 16 images in a shuffled order, 256 tile-aligned 224x224 windows, and the
+whole stream in the other format (the first two with the source's format named
+and, as sub0 / win0, with format 0) -- each beside what a caller had to do before
+(decode_stream_device of the images' tile ranges and encode_stream_device; the
+whole stream decoded, the windows' tiles gathered by torch and encoded; unpack +
+tight pack for JPR1 -> JPT1, decode + encode for JPT1 -> JPR1) and beside a
+device-to-device copy of as many bytes as the call writes.  Every output is
+checked against the baseline's bytes.  The index is built once outside the timed
+calls.  All in this run after the same pre-warm and settle, alternated over
+--rounds rounds, event-timed.  With --once N: N select calls of each kind per
+stream and nothing else."""
 import argparse
 import json
 import os
@@ -735,6 +749,144 @@ def thumb_side(args, torch, jpeg, synth, dev, other):
             del d_stream
 
 
+def select_side(args, torch, jpeg, synth, dev):
+    """Editing the stream (jpegr_select_device) beside decode + encode and a plain copy."""
+    per = jpeg.tiles(CW, CH)
+    nt = CN * per
+    px = CW * CH
+    rng = np.random.default_rng(7)
+    t64 = lambda a: torch.from_numpy(np.asarray(a, np.int64)).to(dev)
+    order = rng.permutation(CN)[:CN // 2]
+    zeros = np.zeros(len(order))
+    sub_cols = [t64(order), t64(zeros), t64(zeros)]
+    wt = CROP // 8                                       # a window's tiles each way
+    wim = rng.integers(0, CN, NCROPS)
+    wx = 8 * rng.integers(0, (CW - CROP) // 8 + 1, NCROPS)
+    wy = 8 * rng.integers(0, (CH - CROP) // 8 + 1, NCROPS)
+    win_cols = [t64(wim), t64(wx), t64(wy)]
+    gw = (CW + 7) // 8
+    oy, ox = np.mgrid[0:wt, 0:wt]
+    d_wtiles = t64(((wim * per + (wy // 8) * gw + wx // 8)[:, None, None] + oy[None] * gw + ox[None]).reshape(-1))
+    all_cols = [t64(np.arange(CN)), t64(np.zeros(CN)), t64(np.zeros(CN))]
+    nsub, nwin = len(order) * per, NCROPS * wt * wt
+    images = {}
+    d_img = torch.empty(CN * px * 4, dtype=torch.uint8, device=dev)
+    synth.rand_rgba_device(d_img, 0, CN * px, seed=1)
+    images["random"] = d_img
+    images["smooth"] = torch.from_numpy(smooth_image(CW, CH)).to(dev).reshape(-1).repeat(CN)
+    d_offs = torch.empty(nt + 1, dtype=torch.int64, device=dev)
+    d_ires = torch.empty(2, dtype=torch.int64, device=dev)
+    iscr = torch.empty(int(jpeg._lib.lib().jpegr_pack_scratch_bytes(nt)), dtype=torch.uint8, device=dev)
+    d_coef = torch.empty(nt * 128, dtype=torch.int16, device=dev)
+    d_res3 = torch.empty(3, dtype=torch.int64, device=dev)
+    ent = jpeg.Entropy(nt, device=dev)
+    d_ures = torch.empty(2, dtype=torch.int64, device=dev)
+    for name, img in images.items():
+        for tight in (False, True):
+            d_stream = jpeg.compress_device(img, CW, CH, CN, tight=tight)
+            n = d_stream.numel()
+            cap = 2 * n                                   # JPR1 from JPT1 is 1.4 to 1.5 times the source
+            jpeg.stream_index_device(d_stream, n, CW, CH, CN, d_offsets=d_offs, d_result=d_ires,
+                                     scratch=iscr)
+            out = {k: torch.empty(cap, dtype=torch.uint8, device=dev) for k in ("sub", "win", "all")}
+            base = {k: torch.empty(cap, dtype=torch.uint8, device=dev) for k in ("sub", "win", "all")}
+            d_copy = torch.empty(cap, dtype=torch.uint8, device=dev)
+            lens = {k: torch.zeros(1, dtype=torch.int64, device=dev) for k in out}
+            blens = {k: torch.zeros(1, dtype=torch.int64, device=dev) for k in out}
+            ress = {k: torch.empty(3, dtype=torch.int64, device=dev) for k in out}
+            bres = torch.empty(2, dtype=torch.int64, device=dev)
+            shapes = {"sub": (sub_cols, CW, CH, tight), "win": (win_cols, CROP, CROP, tight),
+                      "all": (all_cols, CW, CH, not tight),
+                      # the same two with format 0, "the source's": nothing can need re-coding
+                      "sub0": (sub_cols, CW, CH, None), "win0": (win_cols, CROP, CROP, None)}
+            for k in ("sub0", "win0"):
+                out[k] = torch.empty(cap, dtype=torch.uint8, device=dev)
+                lens[k] = torch.zeros(1, dtype=torch.int64, device=dev)
+                ress[k] = torch.empty(3, dtype=torch.int64, device=dev)
+            scr = {k: torch.empty(jpeg.select_scratch_bytes(c[0].numel(), ow, oh), dtype=torch.uint8, device=dev)
+                   for k, (c, ow, oh, _) in shapes.items()}
+            escr = {k: torch.empty(jpeg.stream_encode_scratch_bytes(m, cap), dtype=torch.uint8, device=dev)
+                    for k, m in (("sub", nsub), ("win", nwin), ("all", nt))}
+            pscr = torch.empty(int(jpeg._lib.lib().jpegr_pack_scratch_bytes(nt)), dtype=torch.uint8, device=dev)
+
+            def select(k):
+                cols, ow, oh, tg = shapes[k]
+                jpeg.select_device(d_stream, n, CW, CH, CN, d_offs, *cols, ow, oh, tight=tg, d_out=out[k],
+                                   d_len=lens[k], scratch=scr[k], d_result=ress[k])
+
+            def encode(k, coef, ow, oh, count, tg):
+                jpeg.encode_stream_device(coef, ow, oh, count, tight=tg, d_out=base[k], d_len=blens[k],
+                                          d_result=bres, scratch=escr[k])
+
+            def sub_today():                              # the images' tile ranges, one decode each
+                for i, im in enumerate(order.tolist()):
+                    jpeg.decode_stream_device(d_stream, n, CW, CH, CN, im * per, per,
+                                              d_coef=d_coef[i * per * 128:(i + 1) * per * 128],
+                                              d_result=d_res3, scratch=iscr)
+                encode("sub", d_coef, CW, CH, len(order), tight)
+
+            def win_today():                              # everything decoded, the windows' tiles gathered
+                jpeg.decode_stream_device(d_stream, n, CW, CH, CN, d_coef=d_coef, d_result=d_res3, scratch=iscr)
+                encode("win", d_coef.view(nt, 128)[d_wtiles].view(-1), CROP, CROP, NCROPS, tight)
+
+            def all_today():
+                if tight:                                 # JPT1 -> JPR1: no slot form, decode and encode
+                    jpeg.decode_stream_device(d_stream, n, CW, CH, CN, d_coef=d_coef, d_result=d_res3,
+                                              scratch=iscr)
+                    encode("all", d_coef, CW, CH, CN, False)
+                else:                                     # JPR1 -> JPT1: the slots rebuilt and packed again
+                    jpeg.unpack_device(d_stream, n, CW, CH, CN, ent=ent, d_result=d_ures, scratch=iscr)
+                    jpeg.pack_device(ent, CW, CH, CN, d_out=base["all"], d_len=blens["all"], scratch=pscr,
+                                     tight=True)
+
+            today = {"sub": sub_today, "win": win_today, "all": all_today}
+            if args.once:
+                for _ in range(args.once):
+                    for k in out:
+                        select(k)
+                torch.cuda.synchronize()
+                continue
+            ok, wrote = True, {}
+            for k in ("sub0", "win0"):
+                select(k)
+            for k in today:
+                select(k)
+                today[k]()
+                torch.cuda.synchronize()
+                m = int(lens[k].item())
+                wrote[k] = m
+                ok = ok and m <= cap and m == int(blens[k].item()) and ress[k].cpu().tolist() == [m, -1, 0] \
+                    and bool(torch.equal(out[k][:m], base[k][:m]))
+            for k in ("sub0", "win0"):
+                ok = ok and ress[k].cpu().tolist() == [wrote[k[:3]], -1, 0] \
+                    and bool(torch.equal(out[k][:wrote[k[:3]]], out[k[:3]][:wrote[k[:3]]]))
+            names = {"sub": f"{len(order)} of {CN} images, shuffled", "win": f"{NCROPS} windows of {CROP}x{CROP}",
+                     "all": "whole stream to " + ("JPR1" if tight else "JPT1")}
+            res = {"stream": f"{name} {CN} x {CW}x{CH} {'JPT1' if tight else 'JPR1'}", "tiles": nt,
+                   "stream_bytes": n, "outputs_equal": ok, "steps": args.steps, "rounds": args.rounds,
+                   "what": names, "bytes_written": wrote,
+                   "tiles_written": {"sub": nsub, "win": nwin, "all": nt}}
+            calls = [(k + "_select", lambda k=k: select(k)) for k in ("sub0", "win0")]
+            for k in today:
+                calls += [(k + "_select", lambda k=k: select(k)), (k + "_today", today[k]),
+                          (k + "_copy", lambda k=k: d_copy[:wrote[k]].copy_(out[k][:wrote[k]]))]
+            ms = {k: [] for k, _ in calls}
+            for r in range(args.rounds):                  # alternated; the order turns with the round
+                for key, fn in calls[r % len(calls):] + calls[:r % len(calls)]:
+                    settle(fn, torch.cuda.synchronize, chunk=4)
+                    ms[key].append(timed(fn, args.steps, torch))
+            for key, _ in calls:
+                res[key + "_ms"] = spread(ms[key])
+            med = lambda k: res[k + "_ms"]["median"]
+            for k in today:
+                res[k + "_select_over_today"] = round(med(k + "_select") / med(k + "_today"), 4)
+                res[k + "_select_over_copy"] = round(med(k + "_select") / med(k + "_copy"), 4)
+                res[k + "_select_MB_per_ms"] = round(wrote[k] / 1e6 / med(k + "_select"), 2)
+                res[k + "_copy_MB_per_ms"] = round(wrote[k] / 1e6 / med(k + "_copy"), 2)
+            print(json.dumps(res), flush=True)
+            del d_stream, out, base, d_copy, escr, scr
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=200)
@@ -745,6 +897,7 @@ def main():
     ap.add_argument("--direct", action="store_true")
     ap.add_argument("--crop", action="store_true")
     ap.add_argument("--thumb", action="store_true")
+    ap.add_argument("--select", action="store_true")
     ap.add_argument("--against", default=None,
                     help="with --tight or --direct: a second liblz4jpeg.so to alternate with; "
                          "with --thumb: a second build of jpegr_thumb.hip (make thumb-alt)")
@@ -754,13 +907,15 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("jpeg_pack_bench: needs a GPU (there is no CPU path to time)")
     dev = torch.device("cuda:0")
-    if args.crop or args.thumb:
+    if args.crop or args.thumb or args.select:
         if not args.once:                   # clock pre-warm (bench.py run_lz4)
             d_warm = torch.zeros(256 << 20, dtype=torch.uint8, device=dev)
             settle(lambda: d_warm.add_(1), torch.cuda.synchronize, ms=100.0, chunk=16)
             del d_warm
         if args.crop:
             crop_side(args, torch, jpeg, synth, dev)
+        elif args.select:
+            select_side(args, torch, jpeg, synth, dev)
         else:
             import ctypes
             thumb_side(args, torch, jpeg, synth, dev,

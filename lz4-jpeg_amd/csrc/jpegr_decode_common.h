@@ -2,7 +2,7 @@
 // wave's decode state in LDS, the carry-chain compare, the per-stream walk
 // (decode_stream) and its slow form (decode_stream_slow), each over a source
 // of the stream's bits, and the tail of a wave's stream (the row's 16-B
-// stores, the count of rejected streams).  jpegr_entropy.hip decodes slots
+// stores; the count of rejected streams: wave64.h).  jpegr_entropy.hip decodes slots
 // (SlotBits / SlotTable below: whole 16-B chunks of the stream's slot);
 // jpegr_stream.hip decodes a JPR1 / JPT1 stream (ByteBits below over its
 // StreamSrc: bytes of the lane's own checked record).  One walk, two sources:
@@ -11,6 +11,7 @@
 // kernel, its loads ahead of the walk and its way to publish the count.
 #pragma once
 #include "jpegr_entropy_common.h"
+#include "wave64.h"
 
 namespace {
 
@@ -408,11 +409,6 @@ __device__ __forceinline__ void store_ints(const int16_t *o, int16_t *__restrict
   const uint32_t *src = reinterpret_cast<const uint32_t *>(o);
   for (int v = 0; v < n / 8; ++v)
     d[v] = make_uint4(src[4 * v], src[4 * v + 1], src[4 * v + 2], src[4 * v + 3]);
-}
-
-// The wave's rejected streams, from each lane's count (0 .. 2)
-__device__ __forceinline__ uint32_t wave_rejected(uint32_t fails) {
-  return (uint32_t)__popcll(__ballot(fails & 1)) + 2u * (uint32_t)__popcll(__ballot(fails & 2));
 }
 
 }  // namespace

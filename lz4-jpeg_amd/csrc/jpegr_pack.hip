@@ -30,7 +30,8 @@
 //                            through LDS, records checked and scattered
 // One emit kernel serves both formats: with kTight == false every mode is the
 // constant 0 and what is left is the JPR1 kernel.  The format's
-// pieces, the run and the image's flush are jpegr_pack_common.h's.
+// pieces (the table writes too, which jpegr_select.hip's re-coding shares), the
+// run and the image's flush are jpegr_pack_common.h's.
 // No host-side state, no host read-back: every call can be captured in a graph.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -52,18 +53,6 @@ __global__ __launch_bounds__(256) void jpr_pack_sizes(const uint32_t *__restrict
   tsz[t] = sz;
   put_index(out, cap, t, sz);
   if (t == 0) put_header(out, cap, kMagicJPR1, w, h, nimg);
-}
-
-// the canonical modes of a tile's three streams from the wave's table words
-// (tb[0], tb[1]: Y entries lane, 64 + lane; tb[2]: Cr; tb[3]: Cb), as
-// Y | Cr << 2 | Cb << 4.  Wave-uniform.
-__device__ __forceinline__ uint32_t tile_modes(const uint32_t (&tb)[4], uint32_t n0, uint32_t n1,
-                                               uint32_t n2) {
-  const bool l0 = __ballot(long_len(tb[0]) || long_len(tb[1])) != 0;
-  const bool w0 = __ballot(wide_val(tb[0]) || wide_val(tb[1])) != 0;
-  const bool l1 = __ballot(long_len(tb[2])) != 0, w1 = __ballot(wide_val(tb[2])) != 0;
-  const bool l2 = __ballot(long_len(tb[3])) != 0, w2 = __ballot(wide_val(tb[3])) != 0;
-  return table_mode(n0, l0, w0) | table_mode(n1, l1, w1) << 2 | table_mode(n2, l2, w2) << 4;
 }
 
 // the live table words of a tile on this lane (0 where not live)
@@ -121,11 +110,8 @@ __global__ __launch_bounds__(64 * kPW) void jpt_pack_sizes(
 // before the first is used.  Every byte of the range is written once (the
 // records are dense), by byte stores, so the image needs no zeroing and byte
 // stores to LDS need no atomics.
-// JPT1 writes the table by mode.  Entry k of a stream is on lane k of one
-// register, so the pair (2 j, 2 j + 1) of a length byte never straddles two
-// registers: lane 2 j takes lane 2 j + 1's word by one cross-lane move and
-// writes the byte; with an odd ncodes the last pair's upper lane is not live
-// and holds 0.
+// JPT1 writes the table by mode (put_table_word, jpegr_pack_common.h, as the
+// stream headers' put_stream_headers: jprs_select_emit re-codes with the same).
 template <bool kTight>
 __global__ __launch_bounds__(64 * kPW) void jpr_pack_emit(
     const uint8_t *__restrict__ bits, const uint32_t *__restrict__ meta,
@@ -175,39 +161,11 @@ __global__ __launch_bounds__(64 * kPW) void jpr_pack_emit(
     o[0] = lead + (uint32_t)(toff[h0 + j] - G0);
     o[1] = o[0] + stream_bytes(m[0], 0, md[0]);
     o[2] = o[1] + stream_bytes(m[1], 1, md[1]);
-    if (lane < 12) {                                    // the stream's header, a byte per lane
-      const int c = lane >> 2;
-      const uint32_t mc = c == 0 ? m[0] : c == 1 ? m[1] : m[2];
-      const uint32_t oc = c == 0 ? o[0] : c == 1 ? o[1] : o[2];
-      const uint32_t dc = c == 0 ? md[0] : c == 1 ? md[1] : md[2];
-      const uint32_t hw = stream_header((mc >> 16) & 255u, meta_codes(mc, c), meta_bits(mc, c), dc);
-      img[oc + (lane & 3)] = (uint8_t)(hw >> (8 * (lane & 3)));
-    }
+    put_stream_headers(img, o, m, md, lane);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const int c = q < 2 ? 0 : q - 1;
-      const uint32_t k = (uint32_t)lane + (q == 1 ? 64u : 0u);
-      const uint32_t e = tb[i][q];
-      const uint32_t up = __shfl_down(e, 1);            // lane + 1's word, by every lane of the wave
-      const uint32_t nc = meta_codes(m[c], c);
-      if (k < nc) {
-        uint8_t *p = img + o[c] + 4u;
-        if (md[c] == 0) {                               // i16 value, u8 code length
-          p += 3u * k;
-          p[0] = (uint8_t)e;
-          p[1] = (uint8_t)(e >> 8);
-          p[2] = (uint8_t)(e >> 16);
-        } else {
-          if ((k & 1u) == 0) p[k >> 1] = (uint8_t)(((e >> 16) & 15u) | ((up >> 16) & 15u) << 4);
-          p += (nc + 1u) >> 1;
-          if (md[c] == 1) {
-            p[k] = (uint8_t)e;
-          } else {
-            p[2u * k] = (uint8_t)e;
-            p[2u * k + 1] = (uint8_t)(e >> 8);
-          }
-        }
-      }
+      const int c = word_chan(q);
+      put_table_word(img + o[c] + 4u, meta_codes(m[c], c), md[c], word_entry(q, lane), tb[i][q]);
     }
     const uint32_t mb = bc == 0 ? m[0] : bc == 1 ? m[1] : m[2];
     const uint32_t ob = bc == 0 ? o[0] : bc == 1 ? o[1] : o[2];
@@ -336,10 +294,8 @@ int pack(const void *d_bits, const void *d_meta, const void *d_table, int w, int
          void *d_out, size_t cap, void *d_out_len, void *d_scratch, void *stream) {
   const size_t ntiles = tiles_of(w, h, nimg);
   if (!d_bits || !d_meta || !d_table || !d_out || !d_out_len || !d_scratch || ntiles == 0 ||
-      (reinterpret_cast<uintptr_t>(d_bits) & 3) != 0 || (reinterpret_cast<uintptr_t>(d_meta) & 3) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_table) & 3) != 0 || (reinterpret_cast<uintptr_t>(d_out) & 15) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_out_len) & 7) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_scratch) & 15) != 0)
+      misaligned(d_bits, 3) || misaligned(d_meta, 3) || misaligned(d_table, 3) || misaligned(d_out, 15) ||
+      misaligned(d_out_len, 7) || misaligned(d_scratch, 15))
     return JPEGR_ERR_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const Scratch s = scratch_of(d_scratch, ntiles);
@@ -405,10 +361,8 @@ extern "C" int jpegr_unpack_device(const void *d_in, size_t in_len, int w, int h
                                    void *d_result, void *stream) {
   const size_t ntiles = tiles_of(w, h, nimg);
   if (!d_in || !d_bits || !d_meta || !d_table || !d_scratch || !d_result || ntiles == 0 ||
-      (reinterpret_cast<uintptr_t>(d_bits) & 3) != 0 || (reinterpret_cast<uintptr_t>(d_meta) & 3) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_table) & 3) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_result) & 7) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_scratch) & 15) != 0)
+      misaligned(d_bits, 3) || misaligned(d_meta, 3) || misaligned(d_table, 3) || misaligned(d_result, 7) ||
+      misaligned(d_scratch, 15))
     return JPEGR_ERR_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const Scratch s = scratch_of(d_scratch, ntiles);

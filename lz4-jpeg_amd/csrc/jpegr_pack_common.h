@@ -1,12 +1,15 @@
 // jpegr_pack_common.h -- the JPR stream's format (include/jpegr.h), once, for
 // every reader and writer of it: the record bounds and the slots' fields, the
-// stream header word and the JPT1 table coding, the index and the 16-B header
-// (written and read), the readers' sizes launch (jprs_sizes), the rule that
-// makes a record malformed, the writers' run
-// of 16 tiles and its LDS image's way out to the stream, the scratch layout of
-// jpegr_pack_scratch_bytes, the index scan (lz4r_scan.h as it is) and a
-// workgroup's finish of that scan.  All of it is inlined into its callers; what
-// that does to each kernel's code and time: profiles/jpr_writers_refactor.md.
+// stream header word and the JPT1 table coding (table_bytes, bits_at; written by
+// put_stream_headers, put_table_word, tile_modes), the index and the 16-B header,
+// the readers' first launches (jprs_sizes, sizes_and_scan), the rules for a
+// record (record_rule) and for a caller's offsets (record_at), a range decode's
+// report (RangeReport), the writers' run of 16 tiles and its LDS image's way out,
+// the scratch layout, the index scan (lz4r_scan.h as it is) and its finish by a
+// workgroup (group_offsets) or a wave (scan_record).  The readers' pieces are
+// here, not in a header of their own: each is a few lines on what stands above
+// it.  All of it is inlined; what that does to each kernel's code and time:
+// profiles/jpr_writers_refactor.md, profiles/stream_readers_refactor.md.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -19,6 +22,7 @@
 namespace {
 
 constexpr int kRecMax = 1036;               // 516 + 260 + 260
+constexpr uint32_t kEmptyRec = 12;          // three streams with ncodes = 0, all bytes 0
 constexpr int kHdr = 16;
 constexpr uint32_t kMagicJPR1 = 0x3152504Au;   // "JPR1"
 constexpr uint32_t kMagicJPT1 = 0x3154504Au;   // "JPT1"
@@ -48,6 +52,11 @@ __device__ __forceinline__ uint32_t stream_header(uint32_t rle, uint32_t ncodes,
   return rle | ncodes << 8 | (nbits | md << 14) << 16;
 }
 
+// a stream's first bit byte, its header at offset so: behind its n entries in mode md
+__device__ __forceinline__ uint32_t bits_at(uint32_t so, uint32_t n, uint32_t md) {
+  return so + 4u + table_bytes(n, md);
+}
+
 // a table word's disqualifiers: a length past a nibble, a value past an i8
 // (a word that is not a live entry, 0, disqualifies nothing)
 __device__ __forceinline__ bool long_len(uint32_t e) { return ((e >> 16) & 255u) > 15u; }
@@ -55,6 +64,62 @@ __device__ __forceinline__ bool wide_val(uint32_t e) { return (int16_t)e != (int
 // the writers' canonical JPT1 mode of a table of ncodes entries
 __device__ __forceinline__ uint32_t table_mode(uint32_t ncodes, bool any_long, bool any_wide) {
   return (ncodes == 0 || any_long) ? 0u : any_wide ? 2u : 1u;
+}
+
+// ---- a tile's table on a wave: word k of a stream on lane k ------------------------
+
+// A wave holds a tile's table as four words a lane (value | length << 16; 0 where
+// not live): Y entries lane and 64 + lane, Cr, Cb.  Word q's channel and entry:
+__device__ __forceinline__ int word_chan(int q) { return q < 2 ? 0 : q - 1; }
+__device__ __forceinline__ uint32_t word_entry(int q, int lane) { return (uint32_t)lane + (q == 1 ? 64u : 0u); }
+
+// the canonical modes of a tile's three streams (n0, n1, n2 codes) from those
+// words, as Y | Cr << 2 | Cb << 4.  Wave-uniform.
+__device__ __forceinline__ uint32_t tile_modes(const uint32_t (&tb)[4], uint32_t n0, uint32_t n1,
+                                               uint32_t n2) {
+  const bool l0 = __ballot(long_len(tb[0]) || long_len(tb[1])) != 0;
+  const bool w0 = __ballot(wide_val(tb[0]) || wide_val(tb[1])) != 0;
+  const bool l1 = __ballot(long_len(tb[2])) != 0, w1 = __ballot(wide_val(tb[2])) != 0;
+  const bool l2 = __ballot(long_len(tb[3])) != 0, w2 = __ballot(wide_val(tb[3])) != 0;
+  return table_mode(n0, l0, w0) | table_mode(n1, l1, w1) << 2 | table_mode(n2, l2, w2) << 4;
+}
+
+// a record's three stream headers at img + o[c], from the meta words m (clamped
+// to the slots) and the modes md, a byte per lane
+__device__ __forceinline__ void put_stream_headers(uint8_t *img, const uint32_t (&o)[3], const uint32_t (&m)[3],
+                                                   const uint32_t (&md)[3], int lane) {
+  if (lane < 12) {
+    const int c = lane >> 2;
+    const uint32_t mc = c == 0 ? m[0] : c == 1 ? m[1] : m[2];
+    const uint32_t oc = c == 0 ? o[0] : c == 1 ? o[1] : o[2];
+    const uint32_t dc = c == 0 ? md[0] : c == 1 ? md[1] : md[2];
+    const uint32_t hw = stream_header((mc >> 16) & 255u, meta_codes(mc, c), meta_bits(mc, c), dc);
+    img[oc + (lane & 3)] = (uint8_t)(hw >> (8 * (lane & 3)));
+  }
+}
+
+// This lane's word e, entry k of a table of nc in mode md, to the table at p (a
+// stream's byte 4).  A length byte's pair (2 j, 2 j + 1) is on neighbouring lanes
+// of one register: lane 2 j takes lane 2 j + 1's word (not live: 0).  A whole wave.
+__device__ __forceinline__ void put_table_word(uint8_t *p, uint32_t nc, uint32_t md, uint32_t k, uint32_t e) {
+  const uint32_t up = __shfl_down(e, 1);                // lane + 1's word, by every lane of the wave
+  if (k < nc) {
+    if (md == 0) {                                      // i16 value, u8 code length
+      p += 3u * k;
+      p[0] = (uint8_t)e;
+      p[1] = (uint8_t)(e >> 8);
+      p[2] = (uint8_t)(e >> 16);
+    } else {
+      if ((k & 1u) == 0) p[k >> 1] = (uint8_t)(((e >> 16) & 15u) | ((up >> 16) & 15u) << 4);
+      p += (nc + 1u) >> 1;
+      if (md == 1) {
+        p[k] = (uint8_t)e;
+      } else {
+        p[2u * k] = (uint8_t)e;
+        p[2u * k + 1] = (uint8_t)(e >> 8);
+      }
+    }
+  }
 }
 
 // ---- index and header ---------------------------------------------------------
@@ -151,10 +216,68 @@ __device__ __forceinline__ bool record_rule(Rd rd, uint32_t off, uint32_t size, 
   return ok && p == size;
 }
 
+// Tile t's record by a caller's offsets (ntiles + 1 of them, t < ntiles), which
+// are not trusted: off[t] <= off[t + 1] <= in_len and a record's size, before a
+// byte of it is read.  o0, size: the record, left as they are on a false.
+__device__ __forceinline__ bool record_at(const uint64_t *__restrict__ toff, size_t t, uint64_t in_len,
+                                          uint64_t &o0, uint32_t &size) {
+  const uint64_t a = toff[t], b = toff[t + 1];
+  if (!(a <= b && b <= in_len && b - a >= kEmptyRec && b - a <= (uint64_t)kRecMax)) return false;
+  o0 = a;
+  size = (uint32_t)(b - a);
+  return true;
+}
+
+// How the direct decode and the thumbnails report: malformed(t), a lane whose
+// record (tile t) fails the record rule, the first such tile into result[1];
+// rejected(fails, lane), every lane of a wave with its rejected streams, one add
+// a wave to result[2], after jprs_sizes' zero in stream order.
+struct RangeReport {
+  uint64_t *__restrict__ result;
+  __device__ __forceinline__ void malformed(size_t t) const {
+    atomicMin(reinterpret_cast<unsigned long long *>(result + 1), 1ull + (unsigned long long)t);
+  }
+  __device__ __forceinline__ void rejected(uint32_t fails, int lane) const {
+    const uint32_t f = wave_rejected(fails);
+    if (f && lane == __builtin_ctzll(__ballot(1)))
+      atomicAdd(reinterpret_cast<unsigned long long *>(result + 2), (unsigned long long)f);
+  }
+};
+
 // ---- the scan's finish ----------------------------------------------------------
 
+// A lane's record as the scan gives it: size, and base (the bytes before the
+// wave's first tile) and inc (the wave's sizes up to and with the lane's own).
+// The caller forms the offset where it uses it: summed inside scan_record,
+// ahead of jprs_decode's exit of its idle lanes, that kernel had 24 instructions more.
+struct ScanRec {
+  uint64_t base;
+  uint32_t inc, size;
+  __device__ __forceinline__ uint64_t offset() const { return base + inc - size; }
+};
+
+// A wave, for itself and in registers: the record of tile a + lane, for the 64
+// tiles from tile a of which the range has ntl.  The scan's partial, the group
+// sums before a's group, that group's tiles before a, then a wave scan of the
+// 64 sizes.  All 64 lanes are on; lanes past ntl add 0 and get size 0.
+__device__ __forceinline__ ScanRec scan_record(const int lane, const size_t a, const int ntl,
+                                               const uint32_t *__restrict__ tsz,
+                                               const uint32_t *__restrict__ gsum,
+                                               const uint64_t *__restrict__ part) {
+  const size_t g = a / kGT, g0 = g * kGT;
+  const int skip = (int)(a - g0);
+  const size_t pi = g0 / kPart, gfirst = pi * 64;
+  const uint32_t gs = (gfirst + lane < g) ? gsum[gfirst + lane] : 0u;
+  const uint32_t sk = lane < skip ? tsz[g0 + lane] : 0u;
+  const uint32_t size = lane < ntl ? tsz[a + lane] : 0u;
+  // each sum < 2^32: at most 4,096 tiles of at most 65,535 B
+  const uint64_t base = part[pi] + lane63(wave_incl_add(gs)) + lane63(wave_incl_add(sk));
+  return {base, wave_incl_add(size), size};
+}
+
 // Wave 0: the stream offsets of scan group g's 64 tiles into toff[0..64]
-// (lz4_emit's finish of the scan: partial + earlier group sums + a wave scan).
+// (lz4_emit's finish of the scan: partial + earlier group sums + a wave scan):
+// scan_record without the tiles to skip, an empty scan of 16 instructions.
 __device__ __forceinline__ void group_offsets(const int tid, const size_t g, const size_t ntiles,
                                               const uint32_t *__restrict__ tsz,
                                               const uint32_t *__restrict__ gsum,
@@ -295,5 +418,20 @@ inline void scan(const Scratch &s, size_t ntiles, uint64_t *len, hipStream_t st)
                      (uint64_t)kHdr + 2 * (uint64_t)ntiles, 1, 0, (uint32_t *)nullptr, len,
                      (uint64_t *)nullptr);
 }
+
+// the first launches of a call that reads a stream by its own index: jprs_sizes,
+// then the scan, whose end (the length the index implies) is result[0]
+template <bool kThird>
+inline void sizes_and_scan(const uint8_t *in, size_t in_len, size_t ntiles, int w, int h, int nimg,
+                           const Scratch &s, uint64_t *result, hipStream_t st) {
+  launch_chunks(ntiles, 256, [&](size_t b, unsigned n) {
+    hipLaunchKernelGGL(jprs_sizes<kThird>, dim3(n), dim3(256), 0, st, in, (uint64_t)in_len, ntiles, b * 256,
+                       (uint32_t)w, (uint32_t)h, (uint32_t)nimg, s.tsz, result);
+  });
+  scan(s, ntiles, result, st);
+}
+
+// an entry point's pointer test: p is not aligned to mask + 1 bytes
+inline bool misaligned(const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 
 }  // namespace

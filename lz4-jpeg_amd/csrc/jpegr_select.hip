@@ -26,6 +26,8 @@
 // serves the three cases: every wave reads the 16 header bytes and branches
 // uniformly.  Both passes derive a tile's size from the same bytes by the same
 // functions; the emit pass writes a record only when its size is the scan's.
+// The format's rules are jpegr_pack_common.h's: record_at, record_rule, tile_modes,
+// put_stream_headers and put_table_word (as jpr_pack_emit writes).
 // No host-side state: the call can be captured in a graph.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -37,7 +39,6 @@
 
 namespace {
 
-constexpr uint32_t kEmptyRec = 12;          // three streams with ncodes = 0, all bytes 0
 constexpr int kStage = 1040;                // a record, in whole 16-B chunks
 static_assert(kTW == 4, "a wave's four tiles are spelled out below");
 
@@ -82,11 +83,7 @@ __device__ __forceinline__ int locate(const Sel &s, bool header, uint64_t u, uin
   const uint64_t oy = r / s.ogw, ox = r - oy * s.ogw;
   // y / 8 + ceil(out_h / 8) <= ceil(h / 8), and so for x: t < ntiles
   const uint64_t t = it.image * s.per + ((it.y >> 3) + oy) * s.gw + (it.x >> 3) + ox;
-  const uint64_t a = s.toff[t], b = s.toff[t + 1];
-  if (!(a <= b && b <= s.in_len && b - a >= kEmptyRec && b - a <= (uint64_t)kRecMax)) return 2;
-  o0 = a;
-  size = (uint32_t)(b - a);
-  return 0;
+  return record_at(s.toff, t, s.in_len, o0, size) ? 0 : 2;
 }
 
 __device__ __forceinline__ uint32_t record_bytes(const uint32_t (&m)[3], uint32_t mds) {
@@ -97,38 +94,34 @@ __device__ __forceinline__ uint32_t record_bytes(const uint32_t (&m)[3], uint32_
 // A checked JPR1 record's table words on the wave, as jpr_pack_emit holds a
 // tile's (tb[0], tb[1]: Y entries lane, 64 + lane; tb[2]: Cr; tb[3]: Cb; 0
 // where not live), and from them the writers' canonical modes as
-// Y | Cr << 2 | Cb << 4 (jpegr_pack.hip's tile_modes).  A whole wave.
+// Y | Cr << 2 | Cb << 4 (tile_modes).  A whole wave.
 template <typename Rd>
 __device__ __forceinline__ uint32_t plain_table(Rd rd, const uint32_t (&so)[3], const uint32_t (&m)[3],
                                                 int lane, uint32_t (&tb)[4]) {
-  bool lng[3] = {false, false, false}, wide[3] = {false, false, false};
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    const int c = q < 2 ? 0 : q - 1;
-    const uint32_t k = (uint32_t)lane + (q == 1 ? 64u : 0u);
-    tb[q] = 0u;
-    if (k < (m[c] >> 24)) {
-      const uint32_t x = so[c] + 4u + 3u * k;
-      tb[q] = rd(x) | rd(x + 1) << 8 | rd(x + 2) << 16;
-    }
-    lng[c] = lng[c] || long_len(tb[q]);
-    wide[c] = wide[c] || wide_val(tb[q]);
+    const int c = word_chan(q);
+    const uint32_t k = word_entry(q, lane);
+    const uint32_t x = so[c] + 4u + 3u * k;
+    tb[q] = k < (m[c] >> 24) ? rd(x) | rd(x + 1) << 8 | rd(x + 2) << 16 : 0u;
   }
-  uint32_t mds = 0u;
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-    mds |= table_mode(m[c] >> 24, __ballot(lng[c]) != 0, __ballot(wide[c]) != 0) << (2 * c);
-  return mds;
+  return tile_modes(tb, m[0] >> 24, m[1] >> 24, m[2] >> 24);
 }
 
 // ---- sizes ----------------------------------------------------------------------
 
-// the header, and the result words that the emit pass adds to
-__device__ __forceinline__ void first_tile(const Sel &s, int target, uint8_t *out, uint64_t cap,
-                                           uint64_t *result) {
-  put_header(out, cap, target == JPEGR_STREAM_JPT1 ? kMagicJPT1 : kMagicJPR1, s.out_w, s.out_h, s.nitems);
-  result[1] = ~0ull;
-  result[2] = 0ull;
+// Output tile u's size: the scan's input and the index entry; with tile 0 the
+// header, and the result words that the emit pass adds to.
+__device__ __forceinline__ void put_size(const Sel &s, int target, uint64_t u, uint32_t sz,
+                                         uint32_t *__restrict__ tsz, uint8_t *__restrict__ out, uint64_t cap,
+                                         uint64_t *__restrict__ result) {
+  tsz[u] = sz;
+  put_index(out, cap, u, sz);
+  if (u == 0) {
+    put_header(out, cap, target == JPEGR_STREAM_JPT1 ? kMagicJPT1 : kMagicJPR1, s.out_w, s.out_h, s.nitems);
+    result[1] = ~0ull;
+    result[2] = 0ull;
+  }
 }
 
 __global__ __launch_bounds__(256) void jprs_select_sizes(const Sel s, size_t u_base,
@@ -151,9 +144,7 @@ __global__ __launch_bounds__(256) void jprs_select_sizes(const Sel s, size_t u_b
       if (record_rule<true>(rd, 0u, size, so, m, md)) sz = record_bytes(m, 0u);
     }
   }
-  tsz[u] = sz;
-  put_index(out, cap, u, sz);
-  if (u == 0) first_tile(s, target, out, cap, result);
+  put_size(s, target, u, sz, tsz, out, cap, result);
 }
 
 // ---- a run's source records ------------------------------------------------------
@@ -225,6 +216,14 @@ struct RunRec {
   int ok[kRun];
 };
 
+// tile j's stream offsets and meta words in registers (read from rr at every
+// use, the re-codings took 3.5 to 6 % longer: profiles/stream_readers_refactor.md)
+struct Streams {
+  uint32_t so[3], m[3];
+  __device__ __forceinline__ Streams(const RunRec &rr, int j)
+      : so{rr.so[j][0], rr.so[j][1], rr.so[j][2]}, m{rr.m[j][0], rr.m[j][1], rr.m[j][2]} {}
+};
+
 template <bool kTightSrc>
 __device__ __forceinline__ void rule_run(const RunSrc &run, const uint8_t (*stg)[kStage], int ntl, int tid,
                                          RunRec &rr) {
@@ -265,12 +264,8 @@ __global__ __launch_bounds__(64 * kPW) void jprs_select_sizes_tight(const Sel s,
   locate_run(s, src != 0, t0, ntl, tid, 0, run);
   __syncthreads();
   if (target == src || src == 0) {                      // the same in every workgroup: no re-coding
-    if (tid < ntl) {
-      const uint32_t sz = run.where[tid] == 0 ? run.size[tid] : kEmptyRec;
-      tsz[t0 + tid] = sz;
-      put_index(out, cap, t0 + tid, sz);
-      if (t0 + tid == 0) first_tile(s, target, out, cap, result);
-    }
+    if (tid < ntl)
+      put_size(s, target, t0 + tid, run.where[tid] == 0 ? run.size[tid] : kEmptyRec, tsz, out, cap, result);
     return;
   }
   {
@@ -298,98 +293,70 @@ __global__ __launch_bounds__(64 * kPW) void jprs_select_sizes_tight(const Sel s,
     if (j < ntl && rr.ok[j]) {
       const uint8_t *const rec = stg[j];
       auto rd = [&](uint32_t x) -> uint32_t { return rec[x]; };
-      const uint32_t so[3] = {rr.so[j][0], rr.so[j][1], rr.so[j][2]}, m[3] = {rr.m[j][0], rr.m[j][1], rr.m[j][2]};
+      const Streams r(rr, j);
       uint32_t tb[4];
-      sz[i] = record_bytes(m, plain_table(rd, so, m, lane, tb));
+      sz[i] = record_bytes(r.m, plain_table(rd, r.so, r.m, lane, tb));
     }
   }
   if (lane < kTW && kTW * wv + lane < ntl) {
-    const uint64_t u = t0 + (uint64_t)(kTW * wv + lane);
     const uint32_t mine = lane == 0 ? sz[0] : lane == 1 ? sz[1] : lane == 2 ? sz[2] : sz[3];
-    tsz[u] = mine;
-    put_index(out, cap, u, mine);
-    if (u == 0) first_tile(s, target, out, cap, result);
+    put_size(s, target, t0 + (uint64_t)(kTW * wv + lane), mine, tsz, out, cap, result);
   }
 }
 
 // ---- emit -----------------------------------------------------------------------
 
-// the three stream headers of a record at img + o, modes mds, a byte per lane
-__device__ __forceinline__ void put_stream_headers(uint8_t *img, const uint32_t (&o)[3], const uint32_t (&m)[3],
-                                                   uint32_t mds, int lane) {
-  if (lane < 12) {
-    const int c = lane >> 2;
-    const uint32_t mc = c == 0 ? m[0] : c == 1 ? m[1] : m[2];
-    const uint32_t oc = c == 0 ? o[0] : c == 1 ? o[1] : o[2];
-    const uint32_t hw = stream_header((mc >> 16) & 255u, mc >> 24, mc & 0xFFFFu, (mds >> (2 * c)) & 3u);
-    img[oc + (lane & 3)] = (uint8_t)(hw >> (8 * (lane & 3)));
-  }
+// where a checked record's streams begin in the image, modes omd; their headers
+__device__ __forceinline__ void put_streams(const uint32_t (&m)[3], const uint32_t (&omd)[3], uint8_t *img,
+                                            uint32_t o0, int lane, uint32_t (&o)[3]) {
+  o[0] = o0;
+  o[1] = o[0] + stream_bytes(m[0], 0, omd[0]);
+  o[2] = o[1] + stream_bytes(m[1], 1, omd[1]);
+  put_stream_headers(img, o, m, omd, lane);
 }
 
-// nby bit bytes from the staged record to the image, 64 a round
-__device__ __forceinline__ void put_bits(const uint8_t *from, uint8_t *to, uint32_t nby, int lane) {
-  for (uint32_t b = (uint32_t)lane; b < nby; b += 64u) to[b] = from[b];
+// every stream's bit bytes, staged record (modes smd) to image (omd), 64 a round
+__device__ __forceinline__ void put_bits(const uint8_t *st, const uint32_t (&so)[3], const uint32_t (&m)[3],
+                                         const uint32_t (&smd)[3], const uint32_t (&omd)[3], uint8_t *img,
+                                         const uint32_t (&o)[3], int lane) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const uint8_t *const from = st + bits_at(so[c], m[c] >> 24, smd[c]);
+    uint8_t *const to = img + bits_at(o[c], m[c] >> 24, omd[c]);
+    const uint32_t nby = ((m[c] & 0xFFFFu) + 7u) >> 3;
+    for (uint32_t b = (uint32_t)lane; b < nby; b += 64u) to[b] = from[b];
+  }
 }
 
 // A checked JPR1 record in st -> its JPT1 form at img + o0 (jpr_pack_emit's
-// table writes; the words are plain_table's).
+// table writes; the words and the modes mds are plain_table's).
 __device__ __forceinline__ void emit_tight(const uint8_t *st, const uint32_t (&so)[3], const uint32_t (&m)[3],
                                            const uint32_t (&tb)[4], uint32_t mds, uint8_t *img, uint32_t o0,
                                            int lane) {
-  const uint32_t md[3] = {mds & 3u, (mds >> 2) & 3u, mds >> 4};
+  const uint32_t md[3] = {mds & 3u, (mds >> 2) & 3u, mds >> 4}, plain[3] = {0u, 0u, 0u};
   uint32_t o[3];
-  o[0] = o0;
-  o[1] = o[0] + stream_bytes(m[0], 0, md[0]);
-  o[2] = o[1] + stream_bytes(m[1], 1, md[1]);
-  put_stream_headers(img, o, m, mds, lane);
+  put_streams(m, md, img, o0, lane, o);
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    const int c = q < 2 ? 0 : q - 1;
-    const uint32_t k = (uint32_t)lane + (q == 1 ? 64u : 0u);
-    const uint32_t e = tb[q];
-    const uint32_t up = __shfl_down(e, 1);              // lane + 1's word, by every lane of the wave
-    const uint32_t nc = m[c] >> 24;
-    if (k < nc) {
-      uint8_t *p = img + o[c] + 4u;
-      if (md[c] == 0) {
-        p += 3u * k;
-        p[0] = (uint8_t)e;
-        p[1] = (uint8_t)(e >> 8);
-        p[2] = (uint8_t)(e >> 16);
-      } else {
-        if ((k & 1u) == 0) p[k >> 1] = (uint8_t)(((e >> 16) & 15u) | ((up >> 16) & 15u) << 4);
-        p += (nc + 1u) >> 1;
-        if (md[c] == 1) {
-          p[k] = (uint8_t)e;
-        } else {
-          p[2u * k] = (uint8_t)e;
-          p[2u * k + 1] = (uint8_t)(e >> 8);
-        }
-      }
-    }
+    const int c = word_chan(q);
+    put_table_word(img + o[c] + 4u, m[c] >> 24, md[c], word_entry(q, lane), tb[q]);
   }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const uint32_t nc = m[c] >> 24;
-    put_bits(st + so[c] + 4u + 3u * nc, img + o[c] + 4u + table_bytes(nc, md[c]), ((m[c] & 0xFFFFu) + 7u) >> 3,
-             lane);
-  }
+  put_bits(st, so, m, plain, md, img, o, lane);
 }
 
 // A checked JPT1 record in st (modes mds) -> its JPR1 form at img + o0: modes
-// 1 and 2 expanded to 3-B entries, mode 0 copied.
+// 1 and 2 expanded to 3-B entries (an i8 to its i16), mode 0 copied.  An entry
+// is read a branch a mode: through one reader shared with the thumbnails the call
+// took 2 % longer (profiles/stream_readers_refactor.md).
 __device__ __forceinline__ void emit_plain(const uint8_t *st, const uint32_t (&so)[3], const uint32_t (&m)[3],
                                            uint32_t mds, uint8_t *img, uint32_t o0, int lane) {
-  const uint32_t md[3] = {mds & 3u, (mds >> 2) & 3u, mds >> 4};
+  const uint32_t md[3] = {mds & 3u, (mds >> 2) & 3u, mds >> 4}, plain[3] = {0u, 0u, 0u};
   uint32_t o[3];
-  o[0] = o0;
-  o[1] = o[0] + stream_bytes(m[0], 0, 0u);
-  o[2] = o[1] + stream_bytes(m[1], 1, 0u);
-  put_stream_headers(img, o, m, 0u, lane);
+  put_streams(m, plain, img, o0, lane, o);
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    const int c = q < 2 ? 0 : q - 1;
-    const uint32_t k = (uint32_t)lane + (q == 1 ? 64u : 0u);
+    const int c = word_chan(q);
+    const uint32_t k = word_entry(q, lane);
     const uint32_t nc = m[c] >> 24;
     if (k < nc) {
       const uint8_t *t = st + so[c] + 4u;
@@ -415,12 +382,7 @@ __device__ __forceinline__ void emit_plain(const uint8_t *st, const uint32_t (&s
       p[2] = (uint8_t)len;
     }
   }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const uint32_t nc = m[c] >> 24;
-    put_bits(st + so[c] + 4u + table_bytes(nc, md[c]), img + o[c] + 4u + 3u * nc, ((m[c] & 0xFFFFu) + 7u) >> 3,
-             lane);
-  }
+  put_bits(st, so, m, md, plain, img, o, lane);
 }
 
 // A workgroup's 16 output tiles -> stream bytes [G0, G1).  The run is found by
@@ -492,19 +454,17 @@ __global__ __launch_bounds__(64 * kPW, kRecode ? 4 : 6) void jprs_select_emit(
           if (j < ntl && rr.ok[j]) {
             const uint8_t *const st = stg[j];
             auto rd = [&](uint32_t x) -> uint32_t { return st[x]; };
-            const uint32_t so[3] = {rr.so[j][0], rr.so[j][1], rr.so[j][2]};
-            const uint32_t m[3] = {rr.m[j][0], rr.m[j][1], rr.m[j][2]};
-            mds[i] = plain_table(rd, so, m, lane, tb[i]);
+            const Streams r(rr, j);
+            mds[i] = plain_table(rd, r.so, r.m, lane, tb[i]);
           }
         }
 #pragma unroll
         for (int i = 0; i < kTW; ++i) {
           const int j = kTW * wv + i;
           if (mds[i] == ~0u) continue;
-          const uint32_t so[3] = {rr.so[j][0], rr.so[j][1], rr.so[j][2]};
-          const uint32_t m[3] = {rr.m[j][0], rr.m[j][1], rr.m[j][2]};
-          if (record_bytes(m, mds[i]) == osz[i]) {
-            emit_tight(stg[j], so, m, tb[i], mds[i], img, o[i], lane);
+          const Streams r(rr, j);
+          if (record_bytes(r.m, mds[i]) == osz[i]) {
+            emit_tight(stg[j], r.so, r.m, tb[i], mds[i], img, o[i], lane);
             done[i] = true;
           }
         }
@@ -513,10 +473,9 @@ __global__ __launch_bounds__(64 * kPW, kRecode ? 4 : 6) void jprs_select_emit(
         for (int i = 0; i < kTW; ++i) {
           const int j = kTW * wv + i;
           if (j >= ntl || !rr.ok[j]) continue;
-          const uint32_t so[3] = {rr.so[j][0], rr.so[j][1], rr.so[j][2]};
-          const uint32_t m[3] = {rr.m[j][0], rr.m[j][1], rr.m[j][2]};
-          if (record_bytes(m, 0u) == osz[i]) {
-            emit_plain(stg[j], so, m, rr.md[j], img, o[i], lane);
+          const Streams r(rr, j);
+          if (record_bytes(r.m, 0u) == osz[i]) {
+            emit_plain(stg[j], r.so, r.m, rr.md[j], img, o[i], lane);
             done[i] = true;
           }
         }
@@ -562,11 +521,9 @@ extern "C" int jpegr_select_device(const void *d_in, size_t in_len, int w, int h
   if (!d_in || !d_tile_offsets || !d_items || !d_out || !d_out_len || !d_scratch || !d_result ||
       ntiles == 0 || out_w <= 0 || out_h <= 0 || out_w > w || out_h > h ||
       (format != 0 && format != JPEGR_STREAM_JPR1 && format != JPEGR_STREAM_JPT1) ||
-      in_len < (size_t)kHdr || (reinterpret_cast<uintptr_t>(d_out) & 15) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_scratch) & 15) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_tile_offsets) & 7) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_items) & 7) != 0 || (reinterpret_cast<uintptr_t>(d_out_len) & 7) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_result) & 7) != 0)
+      in_len < (size_t)kHdr || misaligned(d_out, 15) || misaligned(d_scratch, 15) ||
+      misaligned(d_tile_offsets, 7) || misaligned(d_items, 7) || misaligned(d_out_len, 7) ||
+      misaligned(d_result, 7))
     return JPEGR_ERR_ARG;
   const size_t ntout = out_tiles(nitems, out_w, out_h);
   if (ntout == 0) return JPEGR_ERR_ARG;

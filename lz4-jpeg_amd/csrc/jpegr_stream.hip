@@ -2,9 +2,9 @@
 // JPT1 (include/jpegr.h): tiles [tile0, tile0 + ntile) of a stream to
 // coefficients, no slots in between.  The format is the header's, one for the
 // launch: jprs_decode branches once into the record routine of that format
-// (decode_record<kTight>).  The index and header reader and the
-// rule that makes a record malformed are the ones unpack uses
-// (jpegr_pack_common.h: get_index, header_ok, record_rule).
+// (decode_record<kTight>).  What every reader of the stream does
+// is jpegr_pack_common.h's: get_index, header_ok, record_rule, scan_record,
+// record_at, RangeReport, sizes_and_scan.
 //
 //   jprs_sizes    (jpegr_pack_common.h: the thumbnails launch it too)
 //                 index -> u32 sizes (the scan's input), the header verdict in
@@ -69,7 +69,9 @@ struct BitBytes {
 };
 
 // What both walks read of a stream (decode_stream's ByteBits and table head,
-// decode_stream_slow's window / len / entry).  JPR1: U table entries of 3 B.
+// decode_stream_slow's window / len / entry).  The table's layout by mode is
+// spelled here and in jpegr_thumb.hip's stream_dc: through one shared reader
+// jprs_decode grew by 291 instructions.  JPR1: U table entries of 3 B.
 template <bool kTight>
 struct StreamSrc;
 
@@ -185,23 +187,8 @@ __device__ __forceinline__ uint32_t stream_decode_wave(DecLds<kLuma ? 64 : 32, k
   return fails;
 }
 
-// Where decode_record reports.  malformed(t): the luma wave's lane, its record
-// (tile t of the stream) fails the record rule; rejected(fails, lane): every
-// lane of a wave, with the lane's rejected streams.
-// The direct decode: the first malformed tile into result[1], the wave's
-// rejected streams in one add to result[2], after jprs_sizes' zero in stream
-// order.
-struct RangeReport {
-  uint64_t *__restrict__ result;
-  __device__ __forceinline__ void malformed(size_t t) const {
-    atomicMin(reinterpret_cast<unsigned long long *>(result + 1), 1ull + (unsigned long long)t);
-  }
-  __device__ __forceinline__ void rejected(uint32_t fails, int lane) const {
-    const uint32_t f = wave_rejected(fails);
-    if (f && lane == __builtin_ctzll(__ballot(1)))
-      atomicAdd(reinterpret_cast<unsigned long long *>(result + 2), (unsigned long long)f);
-  }
-};
+// Where decode_record reports: the direct decode through RangeReport
+// (jpegr_pack_common.h), which states the two calls.
 // A crop: either failure turns the lane's rectangle bad (stat: its status
 // word) and is counted into result[2], after jprs_crop_init's zero.
 struct CropReport {
@@ -257,21 +244,12 @@ __global__ __launch_bounds__(2 * kLanes) void jprs_decode(
     if (tid == 0) atomicMin(reinterpret_cast<unsigned long long *>(result + 1), 0ull);
     return;
   }
-  // the lane's record: the scan's partial, the group sums before a's group,
-  // that group's tiles before a, then a wave scan of the 64 sizes (each wave
-  // for itself, in registers, all 64 lanes on: lanes past the range add 0)
-  const size_t g = a / kGT, g0 = g * kGT;
-  const int skip = (int)(a - g0);
-  const size_t pi = g0 / kPart, gfirst = pi * 64;
-  const uint32_t gs = (gfirst + lane < g) ? gsum[gfirst + lane] : 0u;
-  const uint32_t sk = lane < skip ? tsz[g0 + lane] : 0u;
-  const uint32_t size = lane < ntl ? tsz[a + lane] : 0u;
-  // each sum < 2^32: at most 4,096 tiles of at most 65,535 B
-  const uint64_t base = part[pi] + lane63(wave_incl_add(gs)) + lane63(wave_incl_add(sk));
-  const uint32_t inc = wave_incl_add(size);
+  // the lane's record (each wave for itself, all 64 lanes on)
+  const ScanRec r = scan_record(lane, a, ntl, tsz, gsum, part);
+  const uint32_t size = r.size;
   if (lane >= ntl) return;
   // implied == in_len: every offset of the scan lies inside the stream
-  const uint8_t *rec = in + (base + inc - size);
+  const uint8_t *rec = in + r.offset();
   int16_t *const tile_out = wg_out + (size_t)lane * 128;
   // the stream's format, from the header jprs_sizes accepted: one for the launch
   if (__builtin_amdgcn_readfirstlane(fmt) == 'T')
@@ -358,13 +336,13 @@ __global__ __launch_bounds__(2 * kLanes) void jprs_crop_decode(
   const uint32_t cy = cell / g.gw, cx = cell - cy * g.gw;
   // inside the image (jprs_crop_init): t < ntiles, so toff[t + 1] is the caller's
   const size_t t = (rc.image * tiles_y + g.ty0 + cy) * tiles_x + g.tx0 + cx;
-  const uint64_t o0 = toff[t], o1 = toff[t + 1];
-  if (!(o0 <= o1 && o1 <= in_len && o1 - o0 >= 12u && o1 - o0 <= (uint64_t)kRecMax)) {
+  uint64_t o0;
+  uint32_t size;
+  if (!record_at(toff, t, in_len, o0, size)) {
     if (wv == 0) CropReport{result, stat}.malformed(t);
     return;
   }
   const uint8_t *rec = in + o0;
-  const uint32_t size = (uint32_t)(o1 - o0);
   int16_t *const tile_out = coef + i * 128;
   const uint32_t fmt = in[2];                         // 'R' or 'T': the header jprs_crop_init accepted
   if (__builtin_amdgcn_readfirstlane(fmt) == 'T')
@@ -379,20 +357,14 @@ extern "C" int jpegr_stream_decode_device(const void *d_in, size_t in_len, int w
                                           void *d_scratch, void *d_result, void *stream) {
   const size_t ntiles = tiles_of(w, h, nimg);
   if (!d_in || !d_coef || !d_scratch || !d_result || ntiles == 0 || ntile == 0 ||
-      tile0 > ntiles || ntile > ntiles - tile0 ||
-      (reinterpret_cast<uintptr_t>(d_coef) & 15) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_result) & 7) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_scratch) & 15) != 0)
+      tile0 > ntiles || ntile > ntiles - tile0 || misaligned(d_coef, 15) || misaligned(d_result, 7) ||
+      misaligned(d_scratch, 15))
     return JPEGR_ERR_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const Scratch s = scratch_of(d_scratch, ntiles);
   auto *in = static_cast<const uint8_t *>(d_in);
   auto *result = static_cast<uint64_t *>(d_result);
-  launch_chunks(ntiles, 256, [&](size_t b, unsigned n) {
-    hipLaunchKernelGGL(jprs_sizes<true>, dim3(n), dim3(256), 0, st, in, (uint64_t)in_len, ntiles, b * 256,
-                       (uint32_t)w, (uint32_t)h, (uint32_t)nimg, s.tsz, result);
-  });
-  scan(s, ntiles, result, st);
+  sizes_and_scan<true>(in, in_len, ntiles, w, h, nimg, s, result, st);
   launch_chunks(ntile, kLanes, [&](size_t b, unsigned n) {
     hipLaunchKernelGGL(jprs_decode, dim3(n), dim3(2 * kLanes), 0, st, in, (uint64_t)in_len, ntiles, tile0,
                        ntile, b, s.tsz, s.gsum, s.part, result, static_cast<int16_t *>(d_coef));
@@ -404,20 +376,14 @@ extern "C" int jpegr_stream_index_device(const void *d_in, size_t in_len, int w,
                                          void *d_tile_offsets, void *d_scratch, void *d_result,
                                          void *stream) {
   const size_t ntiles = tiles_of(w, h, nimg);
-  if (!d_in || !d_tile_offsets || !d_scratch || !d_result || ntiles == 0 ||
-      (reinterpret_cast<uintptr_t>(d_tile_offsets) & 7) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_result) & 7) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_scratch) & 15) != 0)
+  if (!d_in || !d_tile_offsets || !d_scratch || !d_result || ntiles == 0 || misaligned(d_tile_offsets, 7) ||
+      misaligned(d_result, 7) || misaligned(d_scratch, 15))
     return JPEGR_ERR_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const Scratch s = scratch_of(d_scratch, ntiles);
   auto *in = static_cast<const uint8_t *>(d_in);
   auto *result = static_cast<uint64_t *>(d_result);
-  launch_chunks(ntiles, 256, [&](size_t b, unsigned n) {
-    hipLaunchKernelGGL(jprs_sizes<false>, dim3(n), dim3(256), 0, st, in, (uint64_t)in_len, ntiles, b * 256,
-                       (uint32_t)w, (uint32_t)h, (uint32_t)nimg, s.tsz, result);
-  });
-  scan(s, ntiles, result, st);
+  sizes_and_scan<false>(in, in_len, ntiles, w, h, nimg, s, result, st);
   launch_chunks(ntiles, kGT, [&](size_t b, unsigned n) {
     hipLaunchKernelGGL(jprs_index_finish, dim3(n), dim3(kGT), 0, st, s.tsz, s.gsum, s.part, ntiles, b,
                        (uint64_t)in_len, result, static_cast<uint64_t *>(d_tile_offsets));
@@ -444,12 +410,9 @@ extern "C" int jpegr_crop_device(const void *d_in, size_t in_len, int w, int h, 
   const size_t ntiles = tiles_of(w, h, nimg);
   const size_t K = jpegr_crop_items(max_w, max_h);
   if (!d_in || !d_tile_offsets || !d_rects || !d_out || !d_scratch || !d_result || ntiles == 0 ||
-      nrects == 0 || K == 0 || max_w > w || max_h > h || in_len < (size_t)kHdr ||
-      (reinterpret_cast<uintptr_t>(d_rects) & 7) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_tile_offsets) & 7) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_result) & 7) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_scratch) & 15) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_out) & 3) != 0 ||
+      nrects == 0 || K == 0 || max_w > w || max_h > h || in_len < (size_t)kHdr || misaligned(d_rects, 7) ||
+      misaligned(d_tile_offsets, 7) || misaligned(d_result, 7) || misaligned(d_scratch, 15) ||
+      misaligned(d_out, 3) ||
       nrects > kMaxWg * kLanes / K)                   // one launch_chunks pass: 2^28 items
     return JPEGR_ERR_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);

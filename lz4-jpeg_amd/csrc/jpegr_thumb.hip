@@ -6,19 +6,21 @@
 // 1.0: every sample of a plane is round_clamp_u8(aa00 * (dc * T0) + 128), the
 // tile is one colour, and that colour is the thumbnail's pixel.
 //
-//   jprs_sizes, the index scan   (jpegr_pack_common.h, lz4r_scan.h as they
-//                 are) when the caller keeps no offsets; jprs_sizes initialises
-//                 the result words
+//   jprs_sizes, the index scan   (jpegr_pack_common.h: sizes_and_scan) when
+//                 the caller keeps no offsets; jprs_sizes initialises the
+//                 result words
 //   jprs_thumb_init   with the caller's offsets instead: the result words from
 //                 the header and off[ntiles]; no sizes, no scan
 //   jprs_thumb    a wave (a workgroup) per 64 consecutive tiles of the range, a
-//                 lane per tile.  The lane finds its record (the scan finished
-//                 in registers as jprs_decode does, or the caller's offsets,
-//                 which are not trusted), checks it by record_rule, and walks
-//                 each of its three streams only until the first (count >= 1,
-//                 value) pair has its value: decode_stream_slow's search, cut
-//                 off early.  The wave's pixels leave as one 256-B run, its DC
-//                 quads as 512 B.
+//                 lane per tile.  The lane finds its record (scan_record, or
+//                 the caller's offsets, which are not trusted), checks it by
+//                 record_rule, and walks each of its three streams only
+//                 until the first (count >= 1, value) pair has its value:
+//                 decode_stream_slow's search, cut off early.  The wave's
+//                 pixels leave as one 256-B run, its DC quads as 512 B; it
+//                 reports through RangeReport (jpegr_pack_common.h's, as
+//                 scan_record and record_rule; through record_at and a shared
+//                 table reader the call was 0.3 to 1.4 % slower).
 //
 // The record read.  A wave's 64 records are one contiguous span of the stream.
 // JPRS_THUMB_WINDOW = 1 (shipped): the wave copies the span into a 12-KiB LDS
@@ -205,27 +207,17 @@ __global__ __launch_bounds__(kWave) void jprs_thumb(
   uint64_t o0 = 0;
   uint32_t size = 0;
   bool valid = on;
-  if (toff != nullptr) {
+  if (toff != nullptr) {                                        // record_at's rule, spelled here
     if (on) {                                                   // a + lane < ntiles: off[.. + 1] is the caller's
       o0 = toff[a + lane];
       const uint64_t o1 = toff[a + lane + 1];
-      valid = o0 <= o1 && o1 <= in_len && o1 - o0 >= 12u && o1 - o0 <= (uint64_t)kRecMax;
+      valid = o0 <= o1 && o1 <= in_len && o1 - o0 >= kEmptyRec && o1 - o0 <= (uint64_t)kRecMax;
       size = valid ? (uint32_t)(o1 - o0) : 0u;
     }
-  } else {
-    // the scan's partial, the group sums before a's group, that group's tiles
-    // before a, then a wave scan of the 64 sizes (all 64 lanes on: lanes past
-    // the range add 0).  implied == in_len: every offset lies inside the stream
-    const size_t g = a / kGT, g0 = g * kGT;
-    const int skip = (int)(a - g0);
-    const size_t pi = g0 / kPart, gfirst = pi * 64;
-    const uint32_t gs = (gfirst + lane < g) ? gsum[gfirst + lane] : 0u;
-    const uint32_t sk = lane < skip ? tsz[g0 + lane] : 0u;
-    size = on ? tsz[a + lane] : 0u;
-    // each sum < 2^32: at most 4,096 tiles of at most 65,535 B
-    const uint64_t base = part[pi] + lane63(wave_incl_add(gs)) + lane63(wave_incl_add(sk));
-    const uint32_t inc = wave_incl_add(size);
-    o0 = base + inc - size;
+  } else {                                                      // implied == in_len: every offset lies inside the stream
+    const ScanRec r = scan_record(lane, a, ntl, tsz, gsum, part);
+    o0 = r.offset();
+    size = r.size;
   }
   const uint8_t *const rec = in + o0;
   uint32_t roff = 0;
@@ -281,9 +273,9 @@ __global__ __launch_bounds__(kWave) void jprs_thumb(
       good = tight ? record_dc<true>(rd, size, dc, fails) : record_dc<false>(rd, size, dc, fails);
     }
   }
+  const RangeReport rep{result};
   if (on) {
-    if (!good)
-      atomicMin(reinterpret_cast<unsigned long long *>(result + 1), 1ull + (unsigned long long)(a + lane));
+    if (!good) rep.malformed(a + lane);
     if (rgba)
       rgba[first + lane] = rgba_of(dc_sample(dc[0], kYStep, kYAlpha), dc_sample(dc[1], kCStep, kCAlpha),
                                    dc_sample(dc[2], kCStep, kCAlpha));
@@ -291,9 +283,7 @@ __global__ __launch_bounds__(kWave) void jprs_thumb(
       dcq[first + lane] = make_uint2((uint32_t)(uint16_t)dc[0] | (uint32_t)(uint16_t)dc[1] << 16,
                                      (uint32_t)(uint16_t)dc[2]);
   }
-  // the wave's rejected streams (0 .. 3 a lane) in one add, after the first launch's zero
-  const uint32_t f = (uint32_t)__popcll(__ballot(fails & 1)) + 2u * (uint32_t)__popcll(__ballot(fails & 2));
-  if (f && lane == 0) atomicAdd(reinterpret_cast<unsigned long long *>(result + 2), (unsigned long long)f);
+  rep.rejected(fails, lane);                                    // 0 .. 3 a lane, every lane of the wave
 }
 
 }  // namespace
@@ -307,12 +297,8 @@ extern "C" int jpegr_thumb_device(const void *d_in, size_t in_len, int w, int h,
   const size_t ntiles = tiles_of(w, h, nimg);
   if (!d_in || !d_result || (!d_rgba_out && !d_dc_out) || ntiles == 0 || nimage == 0 ||
       image0 > (size_t)nimg || nimage > (size_t)nimg - image0 || in_len < (size_t)kHdr ||
-      (!d_tile_offsets && !d_scratch) ||
-      (reinterpret_cast<uintptr_t>(d_tile_offsets) & 7) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_rgba_out) & 15) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_dc_out) & 7) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_result) & 7) != 0 ||
-      (reinterpret_cast<uintptr_t>(d_scratch) & 15) != 0)
+      (!d_tile_offsets && !d_scratch) || misaligned(d_tile_offsets, 7) || misaligned(d_rgba_out, 15) ||
+      misaligned(d_dc_out, 7) || misaligned(d_result, 7) || misaligned(d_scratch, 15))
     return JPEGR_ERR_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   auto *in = static_cast<const uint8_t *>(d_in);
@@ -325,11 +311,7 @@ extern "C" int jpegr_thumb_device(const void *d_in, size_t in_len, int w, int h,
                        (uint32_t)w, (uint32_t)h, (uint32_t)nimg, toff, result);
   } else {
     s = scratch_of(d_scratch, ntiles);
-    launch_chunks(ntiles, 256, [&](size_t b, unsigned n) {
-      hipLaunchKernelGGL(jprs_sizes<true>, dim3(n), dim3(256), 0, st, in, (uint64_t)in_len, ntiles, b * 256,
-                         (uint32_t)w, (uint32_t)h, (uint32_t)nimg, s.tsz, result);
-    });
-    scan(s, ntiles, result, st);
+    sizes_and_scan<true>(in, in_len, ntiles, w, h, nimg, s, result, st);
   }
   launch_chunks(nimage * per, kWave, [&](size_t b, unsigned n) {
     hipLaunchKernelGGL(jprs_thumb, dim3(n), dim3(kWave), 0, st, in, (uint64_t)in_len, image0 * per,

@@ -43,6 +43,11 @@ __device__ __forceinline__ uint32_t write_lane(uint32_t v, uint32_t s) {
   return v;
 }
 
+// the wave's sum of each lane's 0 .. 3 (the JPEG decoders' rejected streams)
+__device__ __forceinline__ uint32_t wave_rejected(uint32_t fails) {
+  return (uint32_t)__popcll(__ballot(fails & 1)) + 2u * (uint32_t)__popcll(__ballot(fails & 2));
+}
+
 __device__ __forceinline__ int ctz64(uint64_t m) { return __builtin_ctzll(m); }
 
 // lane mask of a predicate, straight from the compare (hip's __ballot goes

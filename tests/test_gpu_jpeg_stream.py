@@ -13,6 +13,7 @@ import pytest
 
 import entropy_inputs as E
 import jpr_format as J
+import jpt_format as T
 from jpr_gpu_lib import (SENTINEL, U64, crafted, crafted_jpr, encoded, encoded_jpr, gpu_decode,
                          jpr_mutations, pack_scratch)
 
@@ -60,6 +61,23 @@ def test_tile_counts(gpu, nt):
         got, res = gpu_decode(data, len(data), dims, tile0, ntile)
         assert res == [len(data), U64, 0], (tile0, ntile)
         assert np.array_equal(got, coef[tile0:tile0 + ntile]), (tile0, ntile)
+
+
+@pytest.mark.parametrize("tight", [False, True], ids=["JPR1", "JPT1"])
+def test_ranges_inside_a_later_scan_partial(gpu, tight):
+    """One stream of 4,160 tiles (a 520 x 512 image), whose second scan partial
+    begins at tile 4,096: a range that crosses into it from six tiles before,
+    one that starts on its first tile, and its last tile alone.  Each equals the
+    same tiles of the whole-stream decode, which equals the encoder's input."""
+    arrays, coef, dims = encoded(4160, 520, 512)
+    data = T.pack(*arrays, *dims) if tight else encoded_jpr(4160, 520, 512)
+    whole, res = gpu_decode(data, len(data), dims)
+    assert res == [len(data), U64, 0]
+    assert np.array_equal(whole, coef)
+    for tile0, ntile in ((4090, 70), (4096, 64), (4159, 1)):
+        got, res = gpu_decode(data, len(data), dims, tile0, ntile)
+        assert res == [len(data), U64, 0], (tile0, ntile)
+        assert np.array_equal(got, whole[tile0:tile0 + ntile]), (tile0, ntile)
 
 
 # ---- three images ----------------------------------------------------------------

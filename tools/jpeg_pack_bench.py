@@ -6,7 +6,8 @@ launches.
 
     python tools/jpeg_pack_bench.py [--steps K] [--once N]
                                     [--decode | --tight [--against LIB] | --direct [--against LIB]
-                                     | --crop | --thumb [--against LIB] | --select]
+                                     | --crop [--against LIB] | --thumb [--against LIB]
+                                     | --select [--against LIB]]
 
 Images: bench.py's 3840x2160 random image (synth.rand_rgba_device, seed 1)
 and a 3840x2160 smooth one (tests/test_gpu_entropy.py's generator).  Prints
@@ -57,8 +58,10 @@ rectangles.  Then one rectangle per image covering the whole image against
 decode + reconstruct of the same images: the price of the crop mapping where
 it has nothing to save.  All in this run after the same pre-warm and settle,
 alternated over --rounds rounds, event-timed; the crops' bytes are checked
-against the gather's.  With --once N: N crop calls per stream and nothing
-else.
+against the gather's.  --against LIB times the index call and both crop calls of
+this build and of a second build of the library in the same rounds, both by the
+same bare C calls, outputs compared, and prints each pair's ratio of the medians.  With --once N: N crop calls per stream and
+nothing else.
 
 --thumb: 1/8-scale thumbnails from the DC terms alone (jpegr_thumb_device), for
 profiles/jpr_thumb_bench.md: --crop's streams (16 images of 1920x1080, random
@@ -71,9 +74,10 @@ not the thumbnail's -- a mean of 64 rounded samples, AC terms included, against
 the one sample of the DC-only tile -- so only the thumbnail paths' bytes are
 checked, against each other and against every eighth pixel of the
 reconstruction of the DC-only coefficients.  Reports each path's stream bytes
-per ms and its ratio to the baseline.  --against LIB adds the same two
-thumbnail calls of a second build of jpegr_thumb.hip (make thumb-alt: the other
-form of the record read) to the same rounds.  All in this run after the same
+per ms and its ratio to the baseline.  --against LIB times the two thumbnail
+calls of this build and of a second build (the whole library, or jpegr_thumb.hip
+alone: make thumb-alt, the other form of the record read) in the same rounds,
+both by the same bare C call.  All in this run after the same
 pre-warm and settle, alternated over --rounds rounds, event-timed.  With
 --once N: N thumbnail calls (offsets kept) per stream and nothing else.
 
@@ -88,8 +92,10 @@ tight pack for JPR1 -> JPT1, decode + encode for JPT1 -> JPR1) and beside a
 device-to-device copy of as many bytes as the call writes.  Every output is
 checked against the baseline's bytes.  The index is built once outside the timed
 calls.  All in this run after the same pre-warm and settle, alternated over
---rounds rounds, event-timed.  With --once N: N select calls of each kind per
-stream and nothing else."""
+--rounds rounds, event-timed.  --against LIB times the five select calls of this
+build and of a second build of the library in the same rounds, both by the same
+bare C call, outputs compared, and prints each pair's ratio of the medians.  With --once N: N select calls of each kind
+per stream and nothing else."""
 import argparse
 import json
 import os
@@ -133,6 +139,28 @@ def timed(fn, steps, torch):
 def spread(xs):
     xs = sorted(xs)
     return {"min": round(xs[0], 4), "median": round(xs[len(xs) // 2], 4), "max": round(xs[-1], 4)}
+
+
+def second_build(path):
+    """A second build of the library, loaded beside the product's."""
+    import ctypes
+    from lz4jpeg import _lib
+    handle = ctypes.CDLL(os.path.abspath(path), mode=ctypes.RTLD_LOCAL)
+    for fname, res, argt in _lib.SIGNATURES:
+        if hasattr(handle, fname):
+            fn = getattr(handle, fname)
+            fn.restype, fn.argtypes = res, argt
+    return handle
+
+
+def checked(rc):
+    assert rc == 0, rc
+
+
+def over_against(res, keys):
+    for key in keys:
+        res[key + "_over_against"] = round(
+            res[key + "_ms"]["median"] / res["against_" + key + "_ms"]["median"], 4)
 
 
 def decode_side(args, torch, jpeg, name, img, d_coef, d_out, n, back, d_res, s2, unpack):
@@ -542,7 +570,7 @@ CW, CH, CN = 1920, 1080, 16                  # --crop: the stream's images
 CROP, NCROPS = 224, 256
 
 
-def crop_side(args, torch, jpeg, synth, dev):
+def crop_side(args, torch, jpeg, synth, dev, other):
     """Crops straight from the stream beside decode-everything-and-gather."""
     nt = CN * jpeg.tiles(CW, CH)
     px = CW * CH
@@ -634,6 +662,40 @@ def crop_side(args, torch, jpeg, synth, dev):
             calls = [("index", index), ("crops", crops), ("index_and_crops", index_and_crops),
                      ("decode_all_and_gather", decode_all_and_gather), ("whole_crops", whole_crops),
                      ("decode_all", decode_all)]
+            paired = ("index", "crops", "whole_crops")
+            if other is not None:         # the three calls of either build by the same bare C calls
+                import ctypes
+                vp = lambda t: ctypes.c_void_p(t.data_ptr())
+                st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+                a_offs, a_ires, a_out, a_wout = (torch.empty_like(t) for t in (d_offs, d_ires, d_out, d_wout))
+                a_res, a_wres = torch.empty_like(d_res), torch.empty_like(d_wres)
+                rects = torch.stack((*cols, d_dst), dim=1).contiguous()
+                wrects = torch.stack((*whole, d_wdst), dim=1).contiguous()
+
+                def index_on(lib, offs, ires):
+                    checked(lib.jpegr_stream_index_device(vp(d_stream), n, CW, CH, CN, vp(offs), vp(iscr),
+                                                          vp(ires), st))
+
+                def crops_on(lib, r, mw, mh, out, res):
+                    checked(lib.jpegr_crop_device(vp(d_stream), n, CW, CH, CN, vp(d_offs), vp(r), r.shape[0],
+                                                  mw, mh, vp(out), out.numel(), vp(cscr), vp(res), st))
+
+                def three(lib, offs, ires, out, res, wout, wres):
+                    return {"index": lambda: index_on(lib, offs, ires),
+                            "crops": lambda: crops_on(lib, rects, CROP, CROP, out, res),
+                            "whole_crops": lambda: crops_on(lib, wrects, CW, CH, wout, wres)}
+
+                mine = three(jpeg._lib.lib(), d_offs, d_ires, d_out, d_res, d_wout, d_wres)
+                theirs = three(other, a_offs, a_ires, a_out, a_res, a_wout, a_wres)
+                calls = [(k, mine.get(k, fn)) for k, fn in calls]
+                calls += [("against_" + k, theirs[k]) for k in paired]
+                for k in paired:
+                    mine[k]()
+                    theirs[k]()
+                torch.cuda.synchronize()
+                res["against_outputs_equal"] = all(
+                    bool(torch.equal(a, b)) for a, b in ((a_offs, d_offs), (a_ires, d_ires), (a_out, d_out),
+                                                         (a_wout, d_wout), (a_res, d_res), (a_wres, d_wres)))
             ms = {k: [] for k, _ in calls}
             for r in range(args.rounds):                  # alternated; the order turns with the round
                 for key, fn in calls[r % len(calls):] + calls[:r % len(calls)]:
@@ -641,6 +703,8 @@ def crop_side(args, torch, jpeg, synth, dev):
                     ms[key].append(timed(fn, args.steps, torch))
             for key, _ in calls:
                 res[key + "_ms"] = spread(ms[key])
+            if other is not None:
+                over_against(res, paired)
             med = lambda k: res[k + "_ms"]["median"]
             res["crops_over_decode_all_and_gather"] = round(med("crops") / med("decode_all_and_gather"), 4)
             res["index_and_crops_over_decode_all_and_gather"] = round(
@@ -669,11 +733,6 @@ def thumb_side(args, torch, jpeg, synth, dev, other):
     d_out, d_out_scan, d_out_alt = (torch.empty(nt * 4, dtype=torch.uint8, device=dev) for _ in range(3))
     d_coef = torch.empty(nt * 128, dtype=torch.int16, device=dev)
     vp = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
-    if other is not None:
-        other.jpegr_thumb_device.restype = ctypes.c_int
-        other.jpegr_thumb_device.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
-                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
-                                             ctypes.c_size_t] + [ctypes.c_void_p] * 5
     for name, img in images.items():
         for tight in (False, True):
             d_stream = jpeg.compress_device(img, CW, CH, CN, tight=tight)
@@ -690,10 +749,10 @@ def thumb_side(args, torch, jpeg, synth, dev, other):
                 jpeg.thumb_device(d_stream, n, CW, CH, CN, d_out=d_out_scan, scratch=iscr,
                                   d_result=d_res_scan)
 
-            def alt(offs):
-                rc = other.jpegr_thumb_device(vp(d_stream), n, CW, CH, CN, vp(d_offs if offs else None), 0,
-                                              CN, vp(d_out_alt), None, vp(iscr), vp(d_res_alt),
-                                              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+            def on(lib, offs, out, res):                  # the C call itself, of either build
+                rc = lib.jpegr_thumb_device(vp(d_stream), n, CW, CH, CN, vp(d_offs if offs else None), 0,
+                                            CN, vp(out), None, vp(iscr), vp(res),
+                                            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
                 assert rc == 0
 
             def decode_all():
@@ -723,10 +782,14 @@ def thumb_side(args, torch, jpeg, synth, dev, other):
                 and d_res_scan.cpu().tolist() == [n, -1, 0] and d_res3.cpu().tolist() == [n, -1, 0]
             calls = [("thumbs", thumbs), ("thumbs_scan", thumbs_scan), ("index", index),
                      ("decode_all_and_pool", decode_all_and_pool), ("decode_all", decode_all)]
-            if other is not None:
-                calls += [("alt_thumbs", lambda: alt(True)), ("alt_thumbs_scan", lambda: alt(False))]
+            if other is not None:                         # both builds' pair by the same bare call
+                mine = jpeg._lib.lib()
+                calls[:2] = [("thumbs", lambda: on(mine, True, d_out, d_res)),
+                             ("thumbs_scan", lambda: on(mine, False, d_out_scan, d_res_scan))]
+                calls += [("alt_thumbs", lambda: on(other, True, d_out_alt, d_res_alt)),
+                          ("alt_thumbs_scan", lambda: on(other, False, d_out_alt, d_res_alt))]
                 for offs in (True, False):
-                    alt(offs)
+                    on(other, offs, d_out_alt, d_res_alt)
                     torch.cuda.synchronize()
                     ok = ok and bool(torch.equal(d_out_alt, d_out)) and d_res_alt.cpu().tolist() == [n, -1, 0]
             del dc_only, want
@@ -745,11 +808,14 @@ def thumb_side(args, torch, jpeg, synth, dev, other):
                 res[key + "_stream_MB_per_ms"] = round(n / 1e6 / med(key), 2)
                 if key != "decode_all_and_pool":
                     res[key + "_over_decode_all_and_pool"] = round(med(key) / med("decode_all_and_pool"), 4)
+            if other is not None:
+                res["thumbs_over_alt"] = round(med("thumbs") / med("alt_thumbs"), 4)
+                res["thumbs_scan_over_alt"] = round(med("thumbs_scan") / med("alt_thumbs_scan"), 4)
             print(json.dumps(res), flush=True)
             del d_stream
 
 
-def select_side(args, torch, jpeg, synth, dev):
+def select_side(args, torch, jpeg, synth, dev, other):
     """Editing the stream (jpegr_select_device) beside decode + encode and a plain copy."""
     per = jpeg.tiles(CW, CH)
     nt = CN * per
@@ -866,10 +932,39 @@ def select_side(args, torch, jpeg, synth, dev):
                    "stream_bytes": n, "outputs_equal": ok, "steps": args.steps, "rounds": args.rounds,
                    "what": names, "bytes_written": wrote,
                    "tiles_written": {"sub": nsub, "win": nwin, "all": nt}}
-            calls = [(k + "_select", lambda k=k: select(k)) for k in ("sub0", "win0")]
+            sel = lambda k: (lambda: select(k))
+            if other is not None:         # the five calls of either build by the same bare C call
+                import ctypes
+                vp = lambda t: ctypes.c_void_p(t.data_ptr())
+                st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+                items = {k: torch.stack(c[0], dim=1).contiguous() for k, c in shapes.items()}
+                theirs = {k: (torch.empty_like(out[k]), torch.zeros_like(lens[k]), torch.empty_like(ress[k]))
+                          for k in shapes}
+
+                def select_on(lib, k, to):
+                    _, ow, oh, tg = shapes[k]
+                    checked(lib.jpegr_select_device(vp(d_stream), n, CW, CH, CN, vp(d_offs), vp(items[k]),
+                                                    items[k].shape[0], ow, oh, 0 if tg is None else 2 if tg else 1,
+                                                    vp(to[0]), to[0].numel(), vp(to[1]), vp(scr[k]), vp(to[2]), st))
+
+                mine = jpeg._lib.lib()
+                sel = lambda k: (lambda: select_on(mine, k, (out[k], lens[k], ress[k])))
+                against = {k: (lambda k=k: select_on(other, k, theirs[k])) for k in shapes}
+            calls = [(k + "_select", sel(k)) for k in ("sub0", "win0")]
             for k in today:
-                calls += [(k + "_select", lambda k=k: select(k)), (k + "_today", today[k]),
+                calls += [(k + "_select", sel(k)), (k + "_today", today[k]),
                           (k + "_copy", lambda k=k: d_copy[:wrote[k]].copy_(out[k][:wrote[k]]))]
+            if other is not None:
+                calls += [("against_" + k + "_select", fn) for k, fn in against.items()]
+                same = True
+                for k in shapes:
+                    sel(k)()
+                    against[k]()
+                    torch.cuda.synchronize()
+                    m = wrote[k[:3]]
+                    same = same and int(theirs[k][1].item()) == m and bool(torch.equal(theirs[k][2], ress[k])) \
+                        and bool(torch.equal(theirs[k][0][:m], out[k][:m]))
+                res["against_outputs_equal"] = same
             ms = {k: [] for k, _ in calls}
             for r in range(args.rounds):                  # alternated; the order turns with the round
                 for key, fn in calls[r % len(calls):] + calls[:r % len(calls)]:
@@ -877,6 +972,8 @@ def select_side(args, torch, jpeg, synth, dev):
                     ms[key].append(timed(fn, args.steps, torch))
             for key, _ in calls:
                 res[key + "_ms"] = spread(ms[key])
+            if other is not None:
+                over_against(res, [k + "_select" for k in shapes])
             med = lambda k: res[k + "_ms"]["median"]
             for k in today:
                 res[k + "_select_over_today"] = round(med(k + "_select") / med(k + "_today"), 4)
@@ -899,8 +996,9 @@ def main():
     ap.add_argument("--thumb", action="store_true")
     ap.add_argument("--select", action="store_true")
     ap.add_argument("--against", default=None,
-                    help="with --tight or --direct: a second liblz4jpeg.so to alternate with; "
-                         "with --thumb: a second build of jpegr_thumb.hip (make thumb-alt)")
+                    help="with --tight, --direct, --crop or --select: a second liblz4jpeg.so to "
+                         "alternate with; with --thumb: that, or a second build of jpegr_thumb.hip "
+                         "alone (make thumb-alt)")
     args = ap.parse_args()
     import torch
     from lz4jpeg import jpeg, synth
@@ -913,14 +1011,12 @@ def main():
             settle(lambda: d_warm.add_(1), torch.cuda.synchronize, ms=100.0, chunk=16)
             del d_warm
         if args.crop:
-            crop_side(args, torch, jpeg, synth, dev)
+            crop_side(args, torch, jpeg, synth, dev, second_build(args.against) if args.against else None)
         elif args.select:
-            select_side(args, torch, jpeg, synth, dev)
+            select_side(args, torch, jpeg, synth, dev, second_build(args.against) if args.against else None)
         else:
             import ctypes
-            thumb_side(args, torch, jpeg, synth, dev,
-                       ctypes.CDLL(os.path.abspath(args.against), mode=ctypes.RTLD_LOCAL)
-                       if args.against else None)
+            thumb_side(args, torch, jpeg, synth, dev, second_build(args.against) if args.against else None)
         return
     nt = jpeg.tiles(W, H)
     images = {}

@@ -35,13 +35,13 @@ CHUNK12_LIB := $(B)/liblz4r_chunk12.so
 CHUNK12_DEFINE := -DLZ4R_CHUNK_LOG2=12
 CHUNK12_HIPFLAGS = $(HIPFLAGS) $(LZ4R_HIPFLAGS) $(CHUNK12_DEFINE)
 HDRS    := include/lz4r.h include/jpegr.h include/lz4jpeg_compat.h include/lz4jpeg_synth.h \
-           $(CSRC)/jpeg_tables.h \
+           $(CSRC)/jpeg_tables.h $(CSRC)/jpeg_tables_dev.h \
            $(CSRC)/wave64.h $(CSRC)/lz4r_prof.h $(CSRC)/lz4r_layout.h $(CSRC)/lz4r_tile_lds.h \
            $(CSRC)/lz4r_tiles.h $(CSRC)/lz4r_matches.h $(CSRC)/lz4r_scan.h $(CSRC)/lz4r_emit.h \
            $(CSRC)/lz4r_dec_layout.h $(CSRC)/lz4r_dec_parse.h $(CSRC)/lz4r_dec_blocks.h \
            $(CSRC)/lz4r_dec_bare.h $(CSRC)/lz4r_dec_read.h $(CSRC)/jpegr_pack_common.h \
            $(CSRC)/jpegr_entropy_common.h $(CSRC)/jpegr_decode_common.h $(CSRC)/jpegr_crop.h \
-           $(CSRC)/jpegr_pixel.h
+           $(CSRC)/jpegr_pixel.h $(CSRC)/jpegr_dct.h $(CSRC)/jpegr_recon.h
 OBJS    := $(B)/lz4r.o $(B)/lz4r_gpudec.o $(B)/lz4r_read.o $(B)/jpegr.o $(B)/jpegr_blocks.o \
            $(B)/jpegr_entropy.o $(B)/jpegr_pack.o $(B)/jpegr_stream.o $(B)/jpegr_stream_enc.o \
            $(B)/jpegr_thumb.o $(B)/jpegr_select.o \
@@ -58,6 +58,9 @@ bin: $(BIN)/LZ4_seq $(BIN)/JPEG_seq $(BIN)/LZ4_seq.exe $(BIN)/JPEG_seq.exe \
 
 $(CSRC)/jpeg_tables.h: $(CSRC)/gen_jpeg_tables.py
 	python3 $< > $@
+
+$(CSRC)/jpeg_tables_dev.h: $(CSRC)/gen_jpeg_tables.py
+	python3 $< dev > $@
 
 $(B)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(B)

@@ -1,8 +1,9 @@
 // jpegr_crop.h -- what the two halves of jpegr_crop_device (include/jpegr.h)
 // agree on: jprs_crop_init / jprs_crop_decode (jpegr_stream.hip) check the
 // rectangles and decode the tiles they touch into the scratch;
-// jpeg_crop_recon_kernel (jpegr.hip) turns the scratch into each rectangle's
-// pixels and counts the verdicts.
+// jpeg_crop_recon_kernel (jpegr_recon.h, compiled in jpegr.hip) turns the
+// scratch into each rectangle's pixels, by the whole-image reconstruction's own
+// dequantisation, IDCT and pixel, and counts the verdicts.
 //
 // A rectangle occupies K = crop_span(max_w) * crop_span(max_h) items.  Item
 // r K + c is cell c of rectangle r's own gw x gh grid of tiles, row-major with
@@ -41,7 +42,7 @@ __device__ __forceinline__ Grid grid_of(const jpegr_rect &rc) {
 
 }  // namespace jpegr_crop
 
-// The reconstruction half (jpegr.hip): d_coef the scratch's items, d_status its
+// The reconstruction half (the launch: jpegr.hip): d_coef the scratch's items, d_status its
 // status words; counts into result[0], atomicMin into result[1].  Not part of
 // the C ABI.
 __attribute__((visibility("hidden"))) int jpegr_crop_recon_launch(

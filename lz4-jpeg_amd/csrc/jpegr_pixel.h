@@ -1,7 +1,10 @@
-// jpegr_pixel.h -- from a plane's fp64 sample to an RGBA8 pixel, once, for every
-// kernel that reconstructs: jpeg_recon_kernel and jpeg_crop_recon_kernel
-// (jpegr.hip, which also clamps the encoder's chroma with clamp_u8) and the
-// thumbnail kernel (jpegr_thumb.hip).  All of it is inlined into its callers.
+// jpegr_pixel.h -- the pixel arithmetic the JPEG kernels share, each piece once:
+// from a plane's fp64 sample to an RGBA8 pixel (round_clamp_u8, colour_term,
+// rgba_of) for every kernel that reconstructs -- jpeg_recon_kernel and
+// jpeg_crop_recon_kernel (jpegr_recon.h), the thumbnail kernel
+// (jpegr_thumb.hip) -- and the reference's forward colour expressions in fp64
+// (ref_y, ref_cr, ref_cb) for the encoder's slow path (jpegr_dct.h) and the
+// reconstruction's untransformed tiles.  All of it is inlined into its callers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -10,6 +13,21 @@ namespace {
 
 __device__ __forceinline__ int clamp_u8(int v) {       // JPEG.c:132-139
   return v < 0 ? 0 : (v > 255 ? 255 : v);
+}
+
+// The reference's forward colour expressions in fp64, in its order of
+// operations: Y = (uint8_t)((0.299 R + 0.587 G) + 0.114 B) (JPEG.c:127; the
+// value lies in [0, 256)), Cr and Cb = clamp((int)(... + 128.0)) (JPEG.c:157,
+// 180).  The encoder evaluates them on the triples its integer path cannot
+// decide, the reconstruction on the tiles the reference never transforms.
+__device__ __forceinline__ int ref_y(unsigned R, unsigned G, unsigned B) {
+  return (int)(uint8_t)(unsigned)(0.299 * (double)R + 0.587 * (double)G + 0.114 * (double)B);
+}
+__device__ __forceinline__ int ref_cr(unsigned R, unsigned G, unsigned B) {
+  return clamp_u8((int)(0.439 * (double)R - 0.368 * (double)G - 0.071 * (double)B + 128.0));
+}
+__device__ __forceinline__ int ref_cb(unsigned R, unsigned G, unsigned B) {
+  return clamp_u8((int)(-0.148 * (double)R - 0.291 * (double)G + 0.439 * (double)B + 128.0));
 }
 
 // (int)round(x) clamped to 0..255 (JPEG.c:440-446).  round() is half away

@@ -136,6 +136,36 @@ def reconstruct(oracle, rgba):
     return out
 
 
+def decode_every_tile(oracle, coef, w, h):
+    """The pixels of decoding EVERY tile of one w x h image's zigzag
+    coefficients (reconstruct_device without d_orig; the reference leaves the
+    tiles at index >= ceil(w h / 64) untransformed): jo_decode_tile per tile,
+    then the reference's colour expressions (JPEG.c:601-603) in fp64 -- the
+    truncated products, the clamp, alpha 255 -- clipped to w x h."""
+    fn = oracle.L.jo_decode_tile
+    fn.argtypes = [_vp, _vp, _vp, _vp]
+    fn.restype = None
+    tx, ty = (w + 7) // 8, (h + 7) // 8
+    coef = np.ascontiguousarray(coef, dtype=np.int16).reshape(ty * tx, 128)
+    y = np.empty((ty, tx, 8, 8), np.uint8)
+    cr = np.empty((ty, tx, 8, 4), np.uint8)
+    cb = np.empty((ty, tx, 8, 4), np.uint8)
+    for i in range(ty * tx):
+        r, c = divmod(i, tx)
+        fn(coef[i].ctypes.data_as(_vp), y[r, c].ctypes.data_as(_vp),
+           cr[r, c].ctypes.data_as(_vp), cb[r, c].ctypes.data_as(_vp))
+    # (ty, tx, 8, n) -> rows of the padded image; column c uses chroma sample c / 2
+    Y = y.transpose(0, 2, 1, 3).reshape(ty * 8, tx * 8).astype(np.float64)
+    Cr = np.repeat(cr.transpose(0, 2, 1, 3).reshape(ty * 8, tx * 4), 2, axis=1).astype(np.float64)
+    Cb = np.repeat(cb.transpose(0, 2, 1, 3).reshape(ty * 8, tx * 4), 2, axis=1).astype(np.float64)
+    R = Y + np.trunc(1.402 * (Cr - 128.0))
+    G = Y - np.trunc(0.344136 * (Cb - 128.0)) - np.trunc(0.714136 * (Cr - 128.0))
+    B = Y + np.trunc(1.772 * (Cb - 128.0))
+    out = np.full((ty * 8, tx * 8, 4), 255, np.uint8)
+    out[..., :3] = np.clip(np.stack([R, G, B], axis=-1), 0, 255)
+    return np.ascontiguousarray(out[:h, :w])
+
+
 def ref_reconstruct(rgba):
     """The reference's own pipeline (JPEG.c main, via oracle/_ref), or None."""
     L = ref_jpeg()

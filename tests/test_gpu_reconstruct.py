@@ -36,6 +36,27 @@ def test_reconstruct_without_orig_decodes_every_tile(gpu, oracle):
     assert np.array_equal(a, b)
 
 
+@pytest.mark.parametrize("w,h,nimg", [(1, 1, 1), (37, 21, 1), (264, 17, 1), (13, 11, 3)])
+def test_reconstruct_without_orig_matches_oracle_tiles(gpu, oracle, w, h, nimg):
+    """d_orig = NULL against the oracle, not against another kernel: every tile
+    through jo_decode_tile, pixels by the reference's fp64 colour expressions
+    (oracle_api.decode_every_tile).  37 x 21 has 15 tiles of which the reference
+    transforms 13, and a width that is no multiple of 4 (dword stores); 264 x 17
+    has 33 tiles a row, so a second strip of one tile; 13 x 11 is a batch."""
+    import torch
+    from lz4jpeg import jpeg
+    imgs = [oracle.rand_image(w, h, seed=40 + i) for i in range(nimg)]
+    d = torch.from_numpy(np.ascontiguousarray(np.stack(imgs))).to(gpu)
+    coef = jpeg.encode_device(d, w, h, nimg=nimg)
+    got = jpeg.reconstruct_device(coef, w, h, nimg=nimg).cpu().numpy().reshape(nimg, h, w, 4)
+    per_image = coef.cpu().numpy().reshape(nimg, -1)
+    for i in range(nimg):
+        want = oracle_api.decode_every_tile(oracle, per_image[i], w, h)
+        assert np.array_equal(got[i], want), i
+        if (w, h) == (37, 21):      # the expectation reaches the two quirk tiles
+            assert not np.array_equal(want, oracle_api.reconstruct(oracle, imgs[i]))
+
+
 def test_reconstruct_batch(gpu, oracle):
     import torch
     from lz4jpeg import jpeg

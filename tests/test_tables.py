@@ -11,15 +11,66 @@ PI = 3.14159265358979323846
 
 
 def test_tables_header_is_generated_output():
-    gen = subprocess.run([sys.executable, os.path.join(CSRC, "gen_jpeg_tables.py")],
-                         capture_output=True, text=True, check=True).stdout
-    assert open(os.path.join(CSRC, "jpeg_tables.h")).read() == gen
+    for args, name in (([], "jpeg_tables.h"), (["dev"], "jpeg_tables_dev.h")):
+        gen = subprocess.run([sys.executable, os.path.join(CSRC, "gen_jpeg_tables.py")] + args,
+                             capture_output=True, text=True, check=True).stdout
+        assert open(os.path.join(CSRC, name)).read() == gen, name
 
 
-def _table(name):
-    src = open(os.path.join(CSRC, "jpeg_tables.h")).read()
-    body = src.split(f"double {name}[")[1].split("};")[0]
+def _table(name, header="jpeg_tables.h"):
+    src = open(os.path.join(CSRC, header)).read()
+    body = src.split(f"double {name}[")[1].split("};")[0].split("= {", 1)[1]
     return [float.fromhex(x) for x in re.findall(r"-?0x[0-9a-f.]+p[+-]\d+", body)]
+
+
+def _ints(name, header="jpeg_tables.h"):
+    src = open(os.path.join(CSRC, header)).read()
+    body = src.split(f"int {name}[")[1].split("};")[0].split("= {", 1)[1]
+    return [int(v) for v in re.findall(r"-?\d+", re.sub(r"//.*", "", body))]
+
+
+DEV = "jpeg_tables_dev.h"
+
+
+def test_device_tables_repeat_the_primary_ones():
+    """The __constant__ copies the kernels load hold the primary tables' values."""
+    for name in ("C8", "AA88", "AA84"):
+        assert _table("d" + name, DEV) == _table(name), name
+    assert _ints("dLQ", DEV) == _ints("LUMA_Q")
+    assert _ints("dCQ", DEV) == _ints("CHROMA_Q")
+    assert (len(_ints("dLQ", DEV)), len(_ints("dCQ", DEV))) == (64, 32)
+
+
+def test_quantiser_fast_path_constants():
+    """K[i] = RN(alpha_u alpha_v * RN(1 / T)): two IEEE double operations."""
+    for k, aa, q, n in (("dLK", "AA88", "LUMA_Q", 64), ("dCK", "AA84", "CHROMA_Q", 32)):
+        K, AA, Q = _table(k, DEV), _table(aa), _ints(q)
+        assert len(K) == len(AA) == len(Q) == n
+        for i in range(n):
+            assert K[i] == AA[i] * (1.0 / Q[i]), (k, i)
+
+
+def test_zigzag_byte_offsets():
+    assert _ints("dZZ8b", DEV) == [2 * p for p in _ints("ZZ8_POS")]
+    assert _ints("dZZ4b", DEV) == [2 * p for p in _ints("ZZ4_POS")]
+    assert (len(_ints("dZZ8b", DEV)), len(_ints("dZZ4b", DEV))) == (64, 32)
+
+
+def test_reconstruction_tables_by_zigzag_position():
+    """For every position z of a tile's 128 zigzagged int16 ([Y 64][Cr 32][Cb 32]):
+    RZn inverts the zigzag of z's plane, RZq and RZa are the step and the alpha
+    product at that natural index."""
+    rzn, rzq, rza = _ints("dRZn", DEV), _table("dRZq", DEV), _table("dRZa", DEV)
+    assert len(rzn) == len(rzq) == len(rza) == 128
+    luma = (_ints("ZZ8_POS"), _ints("LUMA_Q"), _table("AA88"))
+    chroma = (_ints("ZZ4_POS"), _ints("CHROMA_Q"), _table("AA84"))
+    for z in range(128):
+        (pos, q, aa), zp = (luma, z) if z < 64 else (chroma, (z - 64) % 32)
+        n = rzn[z]
+        assert 0 <= n < len(pos) and pos[n] == zp, z
+        assert rzq[z] == float(q[n]) and rza[z] == aa[n], z
+    assert sorted(rzn[:64]) == list(range(64))
+    assert sorted(rzn[64:96]) == sorted(rzn[96:]) == list(range(32))
 
 
 def test_cos_values_match_libm_expression():

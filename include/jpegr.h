@@ -44,7 +44,18 @@ extern "C" {
 size_t jpegr_coef_count(int w, int h);
 
 /* Device API, asynchronous on `stream`.  `nimg` images of identical size,
- * contiguous (image i at d_rgba + i*w*h*4, output at d_out + i*coef_count). */
+ * contiguous (image i at d_rgba + i*w*h*4, output at d_out + i*coef_count).
+ * Geometry, for these two calls and jpegr_reconstruct_device: w, h > 0, nimg
+ * of 1 .. 65,535 (a grid's y extent), and at most 2^31 - 1 workgroups in x --
+ * ceil(h / 8) tile rows times ceil(ceil(w / 8) / 32) strips of 32 tiles.
+ * Pointers: d_rgba 4-B aligned (a pixel is loaded as a dword, four of them as
+ * one 16-B load at dword alignment where w is a multiple of 4; a base that is
+ * 4-B but not 16-B aligned is inside the contract); d_out_i16 16-B aligned
+ * (uint4 stores); d_out_f64 8-B aligned.  A NULL pointer, a geometry outside
+ * the above or a misaligned pointer: JPEGR_ERR_ARG before any HIP call.  No
+ * read leaves the nimg * w * h * 4 input bytes and no write leaves the nimg *
+ * jpegr_coef_count(w, h) output elements, whatever w and h are (pinned with
+ * guard bands by tests/test_gpu_jpeg_geometry.py). */
 int jpegr_encode_device(const void *d_rgba, int w, int h, int nimg,
                         void *d_out_i16, void *stream);
 
@@ -74,7 +85,14 @@ int jpegr_time_device(const void *d_rgba, int w, int h, int nimg,
  * d_coef is jpegr_encode_device's layout.  Tiles at raster index >=
  * ceil(w*h/64) are never transformed by the reference (:1131) and keep their
  * original samples: pass the source image as d_rgba_orig to reproduce that
- * (NULL decodes them like the others).  Asynchronous on `stream`. */
+ * (NULL decodes them like the others).  Asynchronous on `stream`.
+ * d_coef holds any int16 (the stream decoders deliver any): the largest sample
+ * magnitude stays below 2^26, so the rounding is defined for all of them.
+ * Geometry as for jpegr_encode_device.  d_coef 16-B aligned (uint4 loads);
+ * d_rgba_orig, when given, and d_rgba_out 4-B aligned (dword stores, 16-B
+ * stores only where the address allows).  A NULL d_coef or d_rgba_out, a bad
+ * geometry or a misaligned pointer: JPEGR_ERR_ARG before any HIP call.  No
+ * write leaves the nimg * w * h * 4 bytes at d_rgba_out. */
 int jpegr_reconstruct_device(const void *d_coef, const void *d_rgba_orig, int w, int h,
                              int nimg, void *d_rgba_out, void *stream);
 
@@ -89,7 +107,16 @@ int jpegr_reconstruct_device(const void *d_coef, const void *d_rgba_orig, int w,
  *   jpegr_quantize_device: Quantize (JPEG.c:621-629) in place on n doubles,
  *     element i divided by table[i % size] (fp64 table) and truncated.
  *   jpegr_permute_device: out[i] = in[(i/size)*size + perm[i%size]] for n
- *     doubles (zigzag_pattern, JPEG.c:693-728, with perm = its scan order). */
+ *     doubles (zigzag_pattern, JPEG.c:693-728, with perm = its scan order).
+ *     n need not be a multiple of size: elements at and past n are not
+ *     written (nor, by quantize, read); permute reads `in` inside the last
+ *     block it starts, so `in` holds whole blocks.
+ * Pointers: jpegr_planes_device's d_rgba 4-B aligned, its three planes any
+ * alignment; jpegr_dct_blocks_device's d_blocks any alignment, d_out_f64 8-B
+ * aligned; the fp64 arrays of quantize and permute 8-B aligned, d_perm_i32
+ * 4-B aligned.  A NULL pointer, w, h, nblocks or size <= 0, n == 0, a width
+ * other than 8 and 4, a height other than 8, or a misaligned pointer:
+ * JPEGR_ERR_ARG before any HIP call. */
 int jpegr_planes_device(const void *d_rgba, int w, int h, void *d_y, void *d_cr,
                         void *d_cb, void *stream);
 int jpegr_dct_blocks_device(const void *d_blocks, int width, int height, int nblocks,

@@ -65,8 +65,8 @@ struct Geometry {
 
 bool geometry_of(int w, int h, int nimg, int per, Geometry &g) {
   if (w <= 0 || h <= 0 || nimg <= 0 || nimg > 65535) return false;
-  g.tiles_x = (w + 7) / 8;
-  g.tiles_y = (h + 7) / 8;
+  g.tiles_x = (int)(((long long)w + 7) / 8);     // w + 7 may not wrap
+  g.tiles_y = (int)(((long long)h + 7) / 8);
   g.strips = (g.tiles_x + per - 1) / per;
   const long long gx = (long long)g.tiles_y * g.strips;
   if (gx > 0x7fffffffLL) return false;
@@ -74,10 +74,16 @@ bool geometry_of(int w, int h, int nimg, int per, Geometry &g) {
   return true;
 }
 
+// the pointer rules of include/jpegr.h, checked before any HIP call
+bool misaligned(const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+
+// d_rgba: phase 1's loads are dword-aligned (16 B wide where w % 4 == 0); d_out:
+// phase 4's uint4 stores (int16) or the raw DCT's doubles
 int launch(bool raw, const void *d_rgba, int w, int h, int nimg, void *d_out,
            void *stream) {
   Geometry g;
   if (!d_rgba || !d_out || !geometry_of(w, h, nimg, kETiles, g)) return JPEGR_ERR_ARG;
+  if (misaligned(d_rgba, 3) || misaligned(d_out, raw ? 7 : 15)) return JPEGR_ERR_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const auto kernel = raw ? jpeg_strip_kernel<true> : jpeg_strip_kernel<false>;
   hipLaunchKernelGGL(kernel, g.grid, dim3(kEThreads), 0, s, static_cast<const uint8_t *>(d_rgba),
@@ -105,7 +111,7 @@ extern "C" {
 
 size_t jpegr_coef_count(int w, int h) {
   if (w <= 0 || h <= 0) return 0;
-  return (size_t)((w + 7) / 8) * (size_t)((h + 7) / 8) * 128;
+  return (((size_t)w + 7) / 8) * (((size_t)h + 7) / 8) * 128;
 }
 
 int jpegr_encode_device(const void *d_rgba, int w, int h, int nimg, void *d_out,
@@ -159,6 +165,9 @@ int jpegr_reconstruct_device(const void *d_coef, const void *d_rgba_orig, int w,
                              int nimg, void *d_rgba_out, void *stream) {
   Geometry g;
   if (!d_coef || !d_rgba_out || !geometry_of(w, h, nimg, kTiles, g)) return JPEGR_ERR_ARG;
+  // recon_dequant's uint4 loads; store_px4's dword stores (d_rgba_orig may be NULL)
+  if (misaligned(d_coef, 15) || misaligned(d_rgba_orig, 3) || misaligned(d_rgba_out, 3))
+    return JPEGR_ERR_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const auto kernel = d_rgba_orig ? jpeg_recon_kernel<true> : jpeg_recon_kernel<false>;
   hipLaunchKernelGGL(kernel, g.grid, dim3(kThreads), 0, s, static_cast<const int16_t *>(d_coef),

@@ -101,6 +101,9 @@ hipError_t upload() {
 
 unsigned grid_for(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
 
+// the pointer rules of include/jpegr.h, checked before any HIP call
+bool misaligned(const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+
 }  // namespace
 
 extern "C" {
@@ -108,6 +111,7 @@ extern "C" {
 int jpegr_planes_device(const void *d_rgba, int w, int h, void *d_y, void *d_cr, void *d_cb,
                         void *stream) {
   if (!d_rgba || !d_y || !d_cr || !d_cb || w <= 0 || h <= 0) return JPEGR_ERR_ARG;
+  if (misaligned(d_rgba, 3)) return JPEGR_ERR_ARG;          // read as uint32_t; the planes are bytes
   const size_t npx = (size_t)w * (size_t)h;
   if (npx / 256 + 1 > 0x7fffffffULL) return JPEGR_ERR_ARG;
   hipLaunchKernelGGL(planes_kernel, dim3(grid_for(npx, 256)), dim3(256), 0,
@@ -121,6 +125,7 @@ int jpegr_dct_blocks_device(const void *d_blocks, int width, int height, int nbl
                             void *d_out_f64, void *stream) {
   if (!d_blocks || !d_out_f64 || height != 8 || (width != 8 && width != 4) || nblocks <= 0)
     return JPEGR_ERR_ARG;
+  if (misaligned(d_out_f64, 7)) return JPEGR_ERR_ARG;       // the blocks are bytes
   if (upload() != hipSuccess) return JPEGR_ERR_HIP;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (width == 8)
@@ -137,6 +142,7 @@ int jpegr_dct_blocks_device(const void *d_blocks, int width, int height, int nbl
 int jpegr_quantize_device(void *d_coef_f64, const void *d_table_f64, int size, size_t n,
                           void *stream) {
   if (!d_coef_f64 || !d_table_f64 || size <= 0 || n == 0) return JPEGR_ERR_ARG;
+  if (misaligned(d_coef_f64, 7) || misaligned(d_table_f64, 7)) return JPEGR_ERR_ARG;
   if (n / 256 + 1 > 0x7fffffffULL) return JPEGR_ERR_ARG;
   hipLaunchKernelGGL(quantize_kernel, dim3(grid_for(n, 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), static_cast<double *>(d_coef_f64),
@@ -147,6 +153,8 @@ int jpegr_quantize_device(void *d_coef_f64, const void *d_table_f64, int size, s
 int jpegr_permute_device(const void *d_in_f64, void *d_out_f64, const void *d_perm_i32,
                          int size, size_t n, void *stream) {
   if (!d_in_f64 || !d_out_f64 || !d_perm_i32 || size <= 0 || n == 0) return JPEGR_ERR_ARG;
+  if (misaligned(d_in_f64, 7) || misaligned(d_out_f64, 7) || misaligned(d_perm_i32, 3))
+    return JPEGR_ERR_ARG;
   if (n / 256 + 1 > 0x7fffffffULL) return JPEGR_ERR_ARG;
   hipLaunchKernelGGL(permute_kernel, dim3(grid_for(n, 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), static_cast<const double *>(d_in_f64),

@@ -57,6 +57,30 @@ def test_reconstruct_without_orig_matches_oracle_tiles(gpu, oracle, w, h, nimg):
             assert not np.array_equal(want, oracle_api.reconstruct(oracle, imgs[i]))
 
 
+@pytest.mark.parametrize("name", ["pm3", "pm40", "int16", "peak+", "peak-", "flat"])
+def test_reconstruct_coefficients_the_encoder_never_makes(gpu, oracle, name):
+    """The stream decoders deliver any int16: d_orig = NULL on 264 x 16 x 2 (a
+    second strip of one tile) of seeded +-3, +-40 and uniform int16
+    coefficients, of tiles that are zero but for 32767 or -32768 at each of the
+    128 positions, and of tiles that are all 32767 or all -32768
+    (jpeg_pixel_lib.offgrid_classes), against oracle_api.decode_every_tile, the
+    output in a guard arena.  All are defined inputs for the reference (samples
+    below 2^26).  The two small classes must leave a quarter of the R, G, B bytes
+    off the clamps, or they would say nothing about rounding."""
+    import torch
+    import jpeg_pixel_lib as P
+    coef = P.offgrid_classes()[name]
+    want = P.offgrid_expect(oracle, coef)
+    if name in P.ROUNDING_CLASSES:
+        assert P.in_range_share(want) >= 0.25, P.in_range_share(want)
+    w, h = P.OFFGRID_W, P.OFFGRID_H
+    for fill in P.INPUT_FILLS:
+        out = P.run_reconstruct(coef, w, h, P.NIMG, in_fill=fill)
+        torch.cuda.synchronize()
+        bad = out.problem(want, w * h * 4)
+        assert bad is None, f"{name}, input fill 0x{fill:02x}: {bad}"
+
+
 def test_reconstruct_batch(gpu, oracle):
     import torch
     from lz4jpeg import jpeg

@@ -93,6 +93,8 @@ $(CHUNK12_LIB): $(CSRC)/lz4r.hip $(HDRS)
 	$(HIPCC) $(CHUNK12_HIPFLAGS) -shared -o $@ $<
 
 # executables link the objects statically (no liblz4jpeg.so lookup at run time)
+# how JPEG_dec and JPEG_sel open a .jpr file: the executables' alone, not the library's
+JPR_FILE_OBJS := $(B)/jpr_file.o $(B)/read_file.o
 $(BIN)/LZ4_seq: $(B)/lz4_seq.o $(OBJS)
 	@mkdir -p $(BIN)
 	$(HIPCC) --offload-arch=$(ARCH) -o $@ $^
@@ -101,11 +103,11 @@ $(BIN)/JPEG_seq: $(B)/jpeg_seq.o $(B)/png_io.o $(OBJS)
 	@mkdir -p $(BIN)
 	$(HIPCC) --offload-arch=$(ARCH) -o $@ $^ -lz
 
-$(BIN)/JPEG_dec: $(B)/jpeg_dec.o $(B)/png_io.o $(OBJS)
+$(BIN)/JPEG_dec: $(B)/jpeg_dec.o $(B)/png_io.o $(JPR_FILE_OBJS) $(OBJS)
 	@mkdir -p $(BIN)
 	$(HIPCC) --offload-arch=$(ARCH) -o $@ $^ -lz
 
-$(BIN)/JPEG_sel: $(B)/jpeg_sel.o $(OBJS)
+$(BIN)/JPEG_sel: $(B)/jpeg_sel.o $(JPR_FILE_OBJS) $(OBJS)
 	@mkdir -p $(BIN)
 	$(HIPCC) --offload-arch=$(ARCH) -o $@ $^
 
@@ -130,7 +132,7 @@ oracle:
 # ASan + UBSan build of the host C (no HIP) and the oracle restatements,
 # driven by tests/sanitize/sanitize_main.c; tests/test_sanitize.py
 SAN_SRC := tests/sanitize/sanitize_main.c tests/sanitize/cpu_matches.c $(HOST)/lz4r_decode.c \
-           $(HOST)/png_io.c $(HOST)/synth.c $(HOST)/compat_lz4.c \
+           $(HOST)/png_io.c $(HOST)/read_file.c $(HOST)/synth.c $(HOST)/compat_lz4.c \
            oracle/lz4_oracle.c oracle/jpeg_oracle.c oracle/jpeg_entropy_oracle.c
 sanitize: build/sanitize_main
 

@@ -110,6 +110,7 @@ SIGNATURES = [
 ]
 
 _lib = None
+_calls = {}        # name -> (the bound function, the positions of its void * arguments)
 
 
 class LibraryMissing(RuntimeError):
@@ -130,8 +131,60 @@ def lib():
         fn = getattr(handle, name)
         fn.restype = res
         fn.argtypes = args
+        _calls[name] = (fn, tuple(i for i, t in enumerate(args) if t is _vp))
     _lib = handle
     return _lib
+
+
+def _address(x):
+    """What ctypes takes for a void * argument that is no plain address."""
+    try:
+        return x.data_ptr()                  # a torch tensor
+    except AttributeError:
+        pass
+    if hasattr(x, "ctypes"):
+        return x.ctypes.data                 # a numpy array
+    return x                                 # bytes or a ctypes object
+
+
+def call(name, *args, error=None):
+    """The C function `name` on `args`, each void * argument given as a torch
+    tensor, a numpy array, None or what ctypes takes by itself; returns what
+    the function returns.  With `error`, a nonzero return raises
+    error(code, name)."""
+    if _lib is None:
+        lib()
+    fn, pointers = _calls[name]
+    if pointers:
+        args = list(args)
+        for i in pointers:
+            x = args[i]
+            if x is not None and type(x) is not int:      # else NULL or an address: as it is
+                args[i] = _address(x)
+    rc = fn(*args)
+    if error is not None and rc:
+        raise error(rc, name)
+    return rc
+
+
+def stream_arg(stream=None):
+    """The hipStream_t of a torch stream, by default torch's current one."""
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream()
+    return stream.cuda_stream
+
+
+def batch_verdict(d_result, stream, error, code, what):
+    """After a batched call (crops, reads, blocks): d_result's first word, the
+    amount delivered -- or error(code, "<what> <i>") for the first bad item i,
+    which the second word names as 1 + i (all ones: none).  One read-back."""
+    if stream is not None:
+        stream.synchronize()          # the result is written on `stream`, not torch's current one
+    n, bad = (int(x) for x in d_result.cpu().tolist()[:2])
+    if bad != -1:
+        raise error(code, f"{what} {bad - 1}")
+    return n
 
 
 class Lz4Error(RuntimeError):

@@ -6,25 +6,76 @@ Quantize -> zigzag_pattern, per 8x8 tile.  Here one call covers a whole image
 (or a batch); output int16 per tile [Y 64 zz][Cr 32 zz][Cb 32 zz], raster tiles.
 """
 import ctypes
+import functools
 
 import numpy as np
 
 from . import _lib
-from ._lib import JpegError
+from ._lib import JpegError, stream_arg
+
+_call = functools.partial(_lib.call, error=JpegError)      # a nonzero return raises
 
 
 def coef_count(w, h):
-    return int(_lib.lib().jpegr_coef_count(w, h))
+    return int(_lib.call("jpegr_coef_count", w, h))
 
 
 def tiles(w, h):
     return ((w + 7) // 8) * ((h + 7) // 8)
 
 
-def _stream_handle(stream=None):
-    import torch
-    s = stream if stream is not None else torch.cuda.current_stream()
-    return ctypes.c_void_p(s.cuda_stream)
+# ---- what the wrappers below do before and after their calls ----------------------
+def _buffer(t, n, dtype, device, short=None, in_bytes=False, floor=0):
+    """The caller's tensor t or, when that is None, a new one of n `dtype`
+    elements (at least `floor`).  short: the ValueError's text when t holds
+    fewer than n elements -- with in_bytes, fewer bytes than n `dtype` elements
+    take, whatever t's own dtype."""
+    if t is None:
+        import torch
+        return torch.empty(max(n, floor), dtype=dtype, device=device)
+    if short is not None:
+        held, need = (t.numel() * t.element_size(), n * dtype.itemsize) if in_bytes else (t.numel(), n)
+        if held < need:
+            raise ValueError(short)
+    return t
+
+
+def _check_in_len(d_stream, in_len):
+    if in_len > d_stream.numel():
+        raise ValueError("in_len past the end of d_stream")
+
+
+def _check_offsets(d_offsets, ntiles):
+    if d_offsets.numel() < ntiles + 1:
+        raise ValueError("d_offsets smaller than ntiles + 1")
+
+
+def _image_count(first, count, nimg):
+    """count, or with None the images from `first` on; the range lies in the stream."""
+    if count is None:
+        count = nimg - first
+    if first < 0 or count <= 0 or first + count > nimg:
+        raise ValueError("image range outside the stream")
+    return count
+
+
+def _open_stream(d_stream, who, slots=False):
+    """(w, h, nimg, tight) of a stream on the device, its 16 header bytes read
+    back once.  slots: for the slot form, which only JPR1 has (stream_info
+    rejects every other magic)."""
+    if d_stream.numel() < 16:
+        raise JpegError(-1, f"{who}: shorter than a header")
+    hdr = d_stream[:16].cpu().numpy().tobytes()
+    return (*stream_info(hdr), False) if slots else stream_format(hdr)
+
+
+def _raise_on_verdict(who, res):
+    """res: a call's three result words on the host (jpegr.h): [1] the verdict,
+    [2] the rejected entropy streams."""
+    if res[1] != -1:
+        raise JpegError(-1, f"{who}: inconsistent stream (verdict {res[1]})")
+    if res[2] != 0:
+        raise JpegError(-1, f"{who}: malformed entropy stream")
 
 
 def encode_device(d_rgba, w, h, nimg=1, d_out=None, stream=None):
@@ -33,12 +84,8 @@ def encode_device(d_rgba, w, h, nimg=1, d_out=None, stream=None):
     import torch
     if d_rgba.numel() < nimg * w * h * 4:
         raise ValueError("d_rgba smaller than nimg*h*w*4")
-    if d_out is None:
-        d_out = torch.empty(nimg * coef_count(w, h), dtype=torch.int16, device=d_rgba.device)
-    rc = _lib.lib().jpegr_encode_device(ctypes.c_void_p(d_rgba.data_ptr()), w, h, nimg,
-                                        ctypes.c_void_p(d_out.data_ptr()), _stream_handle(stream))
-    if rc != 0:
-        raise JpegError(rc, "jpegr_encode_device")
+    d_out = _buffer(d_out, nimg * coef_count(w, h), torch.int16, d_rgba.device)
+    _call("jpegr_encode_device", d_rgba, w, h, nimg, d_out, stream_arg(stream))
     return d_out
 
 
@@ -46,20 +93,14 @@ def dct_raw_device(d_rgba, w, h, nimg=1, stream=None):
     """Un-quantised fp64 DCT coefficients, row-major per plane, 128 per tile."""
     import torch
     d_out = torch.empty(nimg * coef_count(w, h), dtype=torch.float64, device=d_rgba.device)
-    rc = _lib.lib().jpegr_dct_raw_device(ctypes.c_void_p(d_rgba.data_ptr()), w, h, nimg,
-                                         ctypes.c_void_p(d_out.data_ptr()), _stream_handle(stream))
-    if rc != 0:
-        raise JpegError(rc, "jpegr_dct_raw_device")
+    _call("jpegr_dct_raw_device", d_rgba, w, h, nimg, d_out, stream_arg(stream))
     return d_out
 
 
 def time_device(d_rgba, w, h, nimg, d_out, iters, stream=None):
     ms = ctypes.c_float(0)
-    rc = _lib.lib().jpegr_time_device(ctypes.c_void_p(d_rgba.data_ptr()), w, h, nimg,
-                                      ctypes.c_void_p(d_out.data_ptr()), iters,
-                                      _stream_handle(stream), ctypes.byref(ms))
-    if rc != 0:
-        raise JpegError(rc, "jpegr_time_device")
+    _call("jpegr_time_device", d_rgba, w, h, nimg, d_out, iters, stream_arg(stream),
+          ctypes.byref(ms))
     return ms.value
 
 
@@ -70,10 +111,7 @@ def encode(rgba):
         raise ValueError("rgba must be (h, w, 4) uint8")
     h, w = a.shape[:2]
     out = np.empty(coef_count(w, h), dtype=np.int16)
-    rc = _lib.lib().jpegr_encode(a.ctypes.data_as(ctypes.c_void_p), w, h,
-                                 out.ctypes.data_as(ctypes.c_void_p))
-    if rc != 0:
-        raise JpegError(rc, "jpegr_encode")
+    _call("jpegr_encode", a, w, h, out)
     return out.reshape(-1, 128)
 
 
@@ -84,12 +122,7 @@ def reconstruct_device(d_coef, w, h, nimg=1, d_orig=None, stream=None):
     trailing tiles (see jpegr.h)."""
     import torch
     out = torch.empty(nimg * w * h * 4, dtype=torch.uint8, device=d_coef.device)
-    rc = _lib.lib().jpegr_reconstruct_device(
-        ctypes.c_void_p(d_coef.data_ptr()),
-        ctypes.c_void_p(d_orig.data_ptr() if d_orig is not None else 0), w, h, nimg,
-        ctypes.c_void_p(out.data_ptr()), _stream_handle(stream))
-    if rc != 0:
-        raise JpegError(rc, "jpegr_reconstruct_device")
+    _call("jpegr_reconstruct_device", d_coef, d_orig, w, h, nimg, out, stream_arg(stream))
     return out
 
 
@@ -105,30 +138,20 @@ class Entropy:
         self.bits = torch.zeros(ntiles * 256, dtype=torch.uint8, device=device)
         self.meta = torch.zeros(ntiles * 3, dtype=torch.int32, device=device)
         self.table = torch.zeros(ntiles * 256, dtype=torch.int32, device=device)
-        nscr = _lib.lib().jpegr_entropy_scratch_bytes(ntiles)
+        nscr = _lib.call("jpegr_entropy_scratch_bytes", ntiles)
         self.scratch = torch.empty(nscr, dtype=torch.uint8, device=device)
         self.status = torch.zeros(4, dtype=torch.int32, device=device)
 
     def encode(self, d_coef, stream=None):
         """RLE + per-stream Huffman + encoded bits of every stream
         (JPEG.c:767-1097) from encode_device's coefficients."""
-        rc = _lib.lib().jpegr_entropy_encode_device(
-            ctypes.c_void_p(d_coef.data_ptr()), self.ntiles, ctypes.c_void_p(self.bits.data_ptr()),
-            ctypes.c_void_p(self.meta.data_ptr()), ctypes.c_void_p(self.table.data_ptr()),
-            ctypes.c_void_p(self.scratch.data_ptr()), ctypes.c_void_p(self.status.data_ptr()),
-            _stream_handle(stream))
-        if rc != 0:
-            raise JpegError(rc, "jpegr_entropy_encode_device")
+        _call("jpegr_entropy_encode_device", d_coef, self.ntiles, self.bits, self.meta, self.table,
+              self.scratch, self.status, stream_arg(stream))
 
     def decode(self, d_coef_out, stream=None):
         """bits + tables -> coefficients (decode_huffman + inverse_RLE)."""
-        rc = _lib.lib().jpegr_entropy_decode_device(
-            ctypes.c_void_p(self.bits.data_ptr()), ctypes.c_void_p(self.meta.data_ptr()),
-            ctypes.c_void_p(self.table.data_ptr()), self.ntiles,
-            ctypes.c_void_p(d_coef_out.data_ptr()), ctypes.c_void_p(self.status.data_ptr()),
-            _stream_handle(stream))
-        if rc != 0:
-            raise JpegError(rc, "jpegr_entropy_decode_device")
+        _call("jpegr_entropy_decode_device", self.bits, self.meta, self.table, self.ntiles,
+              d_coef_out, self.status, stream_arg(stream))
 
     def stream(self, tile, c):
         """Host view of one stream: dict(rle_len, table [(value, len)], nbits, bits)."""
@@ -147,12 +170,15 @@ STREAM_JPR1, STREAM_JPT1 = 1, 2           # jpegr_stream_format's formats
 
 
 def pack_bound(w, h, nimg=1):
-    return int(_lib.lib().jpegr_pack_bound(w, h, nimg))
+    return int(_lib.call("jpegr_pack_bound", w, h, nimg))
 
 
-def _pack_scratch(ntiles, device):
+def _pack_scratch(scratch, ntiles, device):
+    """The caller's scratch, or new scratch for a stream of ntiles tiles."""
+    if scratch is not None:
+        return scratch
     import torch
-    return torch.empty(int(_lib.lib().jpegr_pack_scratch_bytes(ntiles)), dtype=torch.uint8,
+    return torch.empty(int(_lib.call("jpegr_pack_scratch_bytes", ntiles)), dtype=torch.uint8,
                        device=device)
 
 
@@ -171,16 +197,9 @@ def pack_device(ent, w, h, nimg=1, d_out=None, stream=None, d_len=None, scratch=
         d_out = torch.empty(pack_bound(w, h, nimg), dtype=torch.uint8, device=dev)
     if d_len is None:
         d_len = torch.zeros(1, dtype=torch.int64, device=dev)
-    if scratch is None:
-        scratch = _pack_scratch(ent.ntiles, dev)
-    fn = _lib.lib().jpegr_pack_tight_device if tight else _lib.lib().jpegr_pack_device
-    rc = fn(
-        ctypes.c_void_p(ent.bits.data_ptr()), ctypes.c_void_p(ent.meta.data_ptr()),
-        ctypes.c_void_p(ent.table.data_ptr()), w, h, nimg, ctypes.c_void_p(d_out.data_ptr()),
-        d_out.numel(), ctypes.c_void_p(d_len.data_ptr()), ctypes.c_void_p(scratch.data_ptr()),
-        _stream_handle(stream))
-    if rc != 0:
-        raise JpegError(rc, "jpegr_pack_tight_device" if tight else "jpegr_pack_device")
+    scratch = _pack_scratch(scratch, ent.ntiles, dev)
+    _call("jpegr_pack_tight_device" if tight else "jpegr_pack_device", ent.bits, ent.meta, ent.table,
+          w, h, nimg, d_out, d_out.numel(), d_len, scratch, stream_arg(stream))
     return d_out, d_len
 
 
@@ -197,49 +216,39 @@ def unpack_device(d_stream, in_len, w, h, nimg=1, ent=None, stream=None, d_resul
         ent = Entropy(nt, device=d_stream.device)
     elif ent.ntiles != nt:
         raise ValueError("ent does not hold nimg * tiles(w, h) tiles")
-    if in_len > d_stream.numel():
-        raise ValueError("in_len past the end of d_stream")
+    _check_in_len(d_stream, in_len)
     if d_result is None:
         d_result = torch.zeros(2, dtype=torch.int64, device=d_stream.device)
-    if scratch is None:
-        scratch = _pack_scratch(nt, d_stream.device)
-    rc = _lib.lib().jpegr_unpack_device(
-        ctypes.c_void_p(d_stream.data_ptr()), in_len, w, h, nimg,
-        ctypes.c_void_p(ent.bits.data_ptr()), ctypes.c_void_p(ent.meta.data_ptr()),
-        ctypes.c_void_p(ent.table.data_ptr()), ctypes.c_void_p(scratch.data_ptr()),
-        ctypes.c_void_p(d_result.data_ptr()), _stream_handle(stream))
-    if rc != 0:
-        raise JpegError(rc, "jpegr_unpack_device")
+    scratch = _pack_scratch(scratch, nt, d_stream.device)
+    _call("jpegr_unpack_device", d_stream, in_len, w, h, nimg, ent.bits, ent.meta, ent.table, scratch,
+          d_result, stream_arg(stream))
     return ent, d_result
 
 
-def stream_info(header_bytes):
-    """(w, h, nimg) of a JPR stream's first 16 bytes; JpegError on a wrong
-    magic or a zero dimension."""
+def _header_ints(name, header_bytes, count):
+    """The `count` ints the C function `name` reads out of a stream's first 16 bytes."""
     hdr = bytes(header_bytes[:16])
     if len(hdr) < 16:
         raise ValueError("a JPR header is 16 bytes")
-    w, h, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    rc = _lib.lib().jpegr_stream_info(ctypes.c_char_p(hdr), ctypes.byref(w), ctypes.byref(h),
-                                      ctypes.byref(n))
-    if rc != 0:
-        raise JpegError(rc, "jpegr_stream_info")
-    return w.value, h.value, n.value
+    out = [ctypes.c_int() for _ in range(count)]
+    _call(name, hdr, *(ctypes.byref(v) for v in out))
+    return [v.value for v in out]
+
+
+# two C functions, so two bodies: each error names the one that judged the header
+def stream_info(header_bytes):
+    """(w, h, nimg) of a JPR stream's first 16 bytes; JpegError on a wrong
+    magic or a zero dimension."""
+    w, h, n = _header_ints("jpegr_stream_info", header_bytes, 3)
+    return w, h, n
 
 
 def stream_format(header_bytes):
     """(w, h, nimg, tight) of the first 16 bytes of a JPR1 (tight False) or
     JPT1 (tight True) stream; JpegError on any other magic or a zero
     dimension."""
-    hdr = bytes(header_bytes[:16])
-    if len(hdr) < 16:
-        raise ValueError("a JPR header is 16 bytes")
-    w, h, n, fmt = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    rc = _lib.lib().jpegr_stream_format(ctypes.c_char_p(hdr), ctypes.byref(w), ctypes.byref(h),
-                                        ctypes.byref(n), ctypes.byref(fmt))
-    if rc != 0:
-        raise JpegError(rc, "jpegr_stream_format")
-    return w.value, h.value, n.value, fmt.value == STREAM_JPT1
+    w, h, n, fmt = _header_ints("jpegr_stream_format", header_bytes, 4)
+    return w, h, n, fmt == STREAM_JPT1
 
 
 def decode_stream_device(d_stream, in_len, w, h, nimg=1, tile0=0, ntiles=None, d_coef=None,
@@ -256,24 +265,16 @@ def decode_stream_device(d_stream, in_len, w, h, nimg=1, tile0=0, ntiles=None, d
     nt = nimg * tiles(w, h)
     if ntiles is None:
         ntiles = nt - tile0
-    if in_len > d_stream.numel():
-        raise ValueError("in_len past the end of d_stream")
+    _check_in_len(d_stream, in_len)
     if tile0 < 0 or ntiles <= 0 or tile0 + ntiles > nt:
         raise ValueError("tile range outside the stream")
-    if d_coef is None:
-        d_coef = torch.empty(ntiles * 128, dtype=torch.int16, device=d_stream.device)
-    elif d_coef.numel() * d_coef.element_size() < ntiles * 256:
-        raise ValueError("d_coef smaller than ntiles * 128 int16")
-    if d_result is None:
-        d_result = torch.empty(3, dtype=torch.int64, device=d_stream.device)
-    if scratch is None:
-        scratch = _pack_scratch(nt, d_stream.device)
-    rc = _lib.lib().jpegr_stream_decode_device(
-        ctypes.c_void_p(d_stream.data_ptr()), in_len, w, h, nimg, tile0, ntiles,
-        ctypes.c_void_p(d_coef.data_ptr()), ctypes.c_void_p(scratch.data_ptr()),
-        ctypes.c_void_p(d_result.data_ptr()), _stream_handle(stream))
-    if rc != 0:
-        raise JpegError(rc, "jpegr_stream_decode_device")
+    dev = d_stream.device
+    d_coef = _buffer(d_coef, ntiles * 128, torch.int16, dev, "d_coef smaller than ntiles * 128 int16",
+                     in_bytes=True)
+    d_result = _buffer(d_result, 3, torch.int64, dev)
+    scratch = _pack_scratch(scratch, nt, dev)
+    _call("jpegr_stream_decode_device", d_stream, in_len, w, h, nimg, tile0, ntiles, d_coef, scratch,
+          d_result, stream_arg(stream))
     return d_coef, d_result
 
 
@@ -285,22 +286,13 @@ def decompress_images_device(d_stream, first=0, count=None):
     decompress_device).  The other images are not touched.  Raises JpegError
     on an inconsistent stream (d_result[1] != ~0) or a rejected entropy stream
     (d_result[2] != 0)."""
-    if d_stream.numel() < 16:
-        raise JpegError(-1, "decompress_images_device: shorter than a header")
-    w, h, nimg, _ = stream_format(d_stream[:16].cpu().numpy().tobytes())
-    if count is None:
-        count = nimg - first
-    if first < 0 or count <= 0 or first + count > nimg:
-        raise ValueError("image range outside the stream")
+    w, h, nimg, _ = _open_stream(d_stream, "decompress_images_device")
+    count = _image_count(first, count, nimg)
     per = tiles(w, h)
     d_coef, d_result = decode_stream_device(d_stream, d_stream.numel(), w, h, nimg, first * per,
                                             count * per)
     out = reconstruct_device(d_coef, w, h, count)
-    res = d_result.cpu().tolist()
-    if res[1] != -1:
-        raise JpegError(-1, f"decompress_images_device: inconsistent stream (verdict {res[1]})")
-    if res[2] != 0:
-        raise JpegError(-1, "decompress_images_device: malformed entropy stream")
+    _raise_on_verdict("decompress_images_device", d_result.cpu().tolist())
     return out, w, h, count
 
 
@@ -316,32 +308,25 @@ def stream_index_device(d_stream, in_len, w, h, nimg=1, d_offsets=None, d_result
     0.  Asynchronous: no read-back."""
     import torch
     nt = nimg * tiles(w, h)
-    if in_len > d_stream.numel():
-        raise ValueError("in_len past the end of d_stream")
+    _check_in_len(d_stream, in_len)
+    dev = d_stream.device
     if d_offsets is None:
-        d_offsets = torch.empty(nt + 1, dtype=torch.int64, device=d_stream.device)
-    elif d_offsets.numel() < nt + 1:
-        raise ValueError("d_offsets smaller than ntiles + 1")
-    if d_result is None:
-        d_result = torch.empty(2, dtype=torch.int64, device=d_stream.device)
-    if scratch is None:
-        scratch = _pack_scratch(nt, d_stream.device)
-    rc = _lib.lib().jpegr_stream_index_device(
-        ctypes.c_void_p(d_stream.data_ptr()), in_len, w, h, nimg,
-        ctypes.c_void_p(d_offsets.data_ptr()), ctypes.c_void_p(scratch.data_ptr()),
-        ctypes.c_void_p(d_result.data_ptr()), _stream_handle(stream))
-    if rc != 0:
-        raise JpegError(rc, "jpegr_stream_index_device")
+        d_offsets = torch.empty(nt + 1, dtype=torch.int64, device=dev)
+    _check_offsets(d_offsets, nt)
+    d_result = _buffer(d_result, 2, torch.int64, dev)
+    scratch = _pack_scratch(scratch, nt, dev)
+    _call("jpegr_stream_index_device", d_stream, in_len, w, h, nimg, d_offsets, scratch, d_result,
+          stream_arg(stream))
     return d_offsets, d_result
 
 
 def crop_items(max_w, max_h):
     """Items a crop occupies in a call with these maxima (jpegr_crop_items)."""
-    return int(_lib.lib().jpegr_crop_items(max_w, max_h))
+    return int(_lib.call("jpegr_crop_items", max_w, max_h))
 
 
 def crop_scratch_bytes(nrects, max_w, max_h):
-    return int(_lib.lib().jpegr_crop_scratch_bytes(nrects, max_w, max_h))
+    return int(_lib.call("jpegr_crop_scratch_bytes", nrects, max_w, max_h))
 
 
 def crop_device(d_stream, in_len, w, h, nimg, d_offsets, d_image, d_x, d_y, d_w, d_h, max_w, max_h,
@@ -371,37 +356,21 @@ def crop_device(d_stream, in_len, w, h, nimg, d_offsets, d_image, d_x, d_y, d_w,
             out_cap = int((d_dst + 4 * d_w * d_h).max().item())
         else:
             out_cap = nrects * 4 * max_w * max_h
-    if d_out is None:
-        d_out = torch.empty(max(out_cap, 4), dtype=torch.uint8, device=d_stream.device)
+    dev = d_stream.device
+    d_out = _buffer(d_out, out_cap, torch.uint8, dev, floor=4)
     if nrects == 0:
         return d_out, d_dst, (0 if check else None)
-    if in_len > d_stream.numel():
-        raise ValueError("in_len past the end of d_stream")
-    if d_offsets.numel() < nimg * tiles(w, h) + 1:
-        raise ValueError("d_offsets smaller than ntiles + 1")
+    _check_in_len(d_stream, in_len)
+    _check_offsets(d_offsets, nimg * tiles(w, h))
     d_rects = torch.stack((d_image, d_x, d_y, d_w, d_h, d_dst), dim=1).contiguous()
-    need = crop_scratch_bytes(nrects, max_w, max_h)
-    if scratch is None:
-        scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=d_stream.device)
-    elif scratch.numel() < need:
-        raise ValueError("scratch smaller than crop_scratch_bytes(nrects, max_w, max_h)")
-    if d_result is None:
-        d_result = torch.empty(3, dtype=torch.int64, device=d_stream.device)
-    rc = _lib.lib().jpegr_crop_device(
-        ctypes.c_void_p(d_stream.data_ptr()), in_len, w, h, nimg,
-        ctypes.c_void_p(d_offsets.data_ptr()), ctypes.c_void_p(d_rects.data_ptr()), nrects,
-        max_w, max_h, ctypes.c_void_p(d_out.data_ptr()), out_cap,
-        ctypes.c_void_p(scratch.data_ptr()), ctypes.c_void_p(d_result.data_ptr()),
-        _stream_handle(stream))
-    if rc != 0:
-        raise JpegError(rc, "jpegr_crop_device")
+    scratch = _buffer(scratch, crop_scratch_bytes(nrects, max_w, max_h), torch.uint8, dev,
+                      "scratch smaller than crop_scratch_bytes(nrects, max_w, max_h)", floor=16)
+    d_result = _buffer(d_result, 3, torch.int64, dev)
+    _call("jpegr_crop_device", d_stream, in_len, w, h, nimg, d_offsets, d_rects, nrects, max_w, max_h,
+          d_out, out_cap, scratch, d_result, stream_arg(stream))
     if not check:
         return d_out, d_dst, None
-    if stream is not None:
-        stream.synchronize()          # the result is written on `stream`, not torch's current one
-    n, bad, _ = (int(x) for x in d_result.cpu().tolist())
-    if bad != -1:
-        raise JpegError(-1, f"jpegr_crop_device: rectangle {bad - 1}")
+    n = _lib.batch_verdict(d_result, stream, JpegError, -1, "jpegr_crop_device: rectangle")
     return d_out, d_dst, n
 
 
@@ -421,36 +390,22 @@ def thumb_device(d_stream, in_len, w, h, nimg, first=0, count=None, d_offsets=No
     [2] the streams rejected inside the prefix examined (jpegr.h).
     Asynchronous: no read-back."""
     import torch
-    if count is None:
-        count = nimg - first
-    if first < 0 or count <= 0 or first + count > nimg:
-        raise ValueError("image range outside the stream")
-    if in_len > d_stream.numel():
-        raise ValueError("in_len past the end of d_stream")
+    count = _image_count(first, count, nimg)
+    _check_in_len(d_stream, in_len)
     nt, n = nimg * tiles(w, h), count * tiles(w, h)
     dev = d_stream.device
-    if d_offsets is not None and d_offsets.numel() < nt + 1:
-        raise ValueError("d_offsets smaller than ntiles + 1")
-    if d_dc is None and want_dc:
-        d_dc = torch.empty(n * 4, dtype=torch.int16, device=dev)
-    elif d_dc is not None and d_dc.numel() * d_dc.element_size() < n * 8:
-        raise ValueError("d_dc smaller than four int16 per tile")
-    if d_out is None:
-        d_out = torch.empty(n * 4, dtype=torch.uint8, device=dev)
-    elif d_out.numel() * d_out.element_size() < n * 4:
-        raise ValueError("d_out smaller than four bytes per tile")
-    if d_result is None:
-        d_result = torch.empty(3, dtype=torch.int64, device=dev)
-    if scratch is None and d_offsets is None:
-        scratch = _pack_scratch(nt, dev)
-    rc = _lib.lib().jpegr_thumb_device(
-        ctypes.c_void_p(d_stream.data_ptr()), in_len, w, h, nimg,
-        ctypes.c_void_p(d_offsets.data_ptr() if d_offsets is not None else 0), first, count,
-        ctypes.c_void_p(d_out.data_ptr()), ctypes.c_void_p(d_dc.data_ptr() if d_dc is not None else 0),
-        ctypes.c_void_p(scratch.data_ptr() if scratch is not None else 0),
-        ctypes.c_void_p(d_result.data_ptr()), _stream_handle(stream))
-    if rc != 0:
-        raise JpegError(rc, "jpegr_thumb_device")
+    if d_offsets is not None:
+        _check_offsets(d_offsets, nt)
+    if d_dc is not None or want_dc:
+        d_dc = _buffer(d_dc, n * 4, torch.int16, dev, "d_dc smaller than four int16 per tile",
+                       in_bytes=True)
+    d_out = _buffer(d_out, n * 4, torch.uint8, dev, "d_out smaller than four bytes per tile",
+                    in_bytes=True)
+    d_result = _buffer(d_result, 3, torch.int64, dev)
+    if d_offsets is None:
+        scratch = _pack_scratch(scratch, nt, dev)
+    _call("jpegr_thumb_device", d_stream, in_len, w, h, nimg, d_offsets, first, count, d_out, d_dc,
+          scratch, d_result, stream_arg(stream))
     return d_out, d_dc, d_result
 
 
@@ -459,11 +414,7 @@ def _thumbnails(d_stream, w, h, nimg, first, count, d_offsets):
         count = nimg - first
     d_out, _, d_result = thumb_device(d_stream, d_stream.numel(), w, h, nimg, first, count,
                                       d_offsets=d_offsets)
-    res = d_result.cpu().tolist()
-    if res[1] != -1:
-        raise JpegError(-1, f"thumbnails: inconsistent stream (verdict {res[1]})")
-    if res[2] != 0:
-        raise JpegError(-1, "thumbnails: malformed entropy stream")
+    _raise_on_verdict("thumbnails", d_result.cpu().tolist())
     return d_out.view(count, (h + 7) // 8, (w + 7) // 8, 4), w, h, count
 
 
@@ -476,15 +427,13 @@ def thumbnails_device(d_stream, first=0, count=None):
     images are not touched.  Raises JpegError on an inconsistent stream
     (d_result[1] != ~0) or a stream rejected before its DC (d_result[2] != 0),
     as decompress_images_device does."""
-    if d_stream.numel() < 16:
-        raise JpegError(-1, "thumbnails_device: shorter than a header")
-    w, h, nimg, _ = stream_format(d_stream[:16].cpu().numpy().tobytes())
+    w, h, nimg, _ = _open_stream(d_stream, "thumbnails_device")
     return _thumbnails(d_stream, w, h, nimg, first, count, None)
 
 
 # -- editing a stream without decoding it ------------------------------------------
 def select_scratch_bytes(nitems, out_w, out_h):
-    return int(_lib.lib().jpegr_select_scratch_bytes(nitems, out_w, out_h))
+    return int(_lib.call("jpegr_select_scratch_bytes", nitems, out_w, out_h))
 
 
 def _format_arg(tight):
@@ -511,10 +460,8 @@ def select_device(d_stream, in_len, w, h, nimg, d_offsets, d_image, d_x, d_y, ou
     nitems = d_image.numel()
     if nitems == 0 or d_x.numel() != nitems or d_y.numel() != nitems:
         raise ValueError("d_image, d_x and d_y hold one entry per item, and at least one")
-    if in_len > d_stream.numel():
-        raise ValueError("in_len past the end of d_stream")
-    if d_offsets.numel() < nimg * tiles(w, h) + 1:
-        raise ValueError("d_offsets smaller than ntiles + 1")
+    _check_in_len(d_stream, in_len)
+    _check_offsets(d_offsets, nimg * tiles(w, h))
     dev = d_stream.device
     d_items = torch.stack((d_image, d_x, d_y), dim=1).contiguous()
     if d_out is None:
@@ -525,21 +472,11 @@ def select_device(d_stream, in_len, w, h, nimg, d_offsets, d_image, d_x, d_y, ou
         raise ValueError("cap past the end of d_out")
     if d_len is None:
         d_len = torch.zeros(1, dtype=torch.int64, device=dev)
-    if d_result is None:
-        d_result = torch.empty(3, dtype=torch.int64, device=dev)
-    need = select_scratch_bytes(nitems, out_w, out_h)
-    if scratch is None:
-        scratch = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    elif scratch.numel() < need:
-        raise ValueError("scratch smaller than select_scratch_bytes(nitems, out_w, out_h)")
-    rc = _lib.lib().jpegr_select_device(
-        ctypes.c_void_p(d_stream.data_ptr()), in_len, w, h, nimg,
-        ctypes.c_void_p(d_offsets.data_ptr()), ctypes.c_void_p(d_items.data_ptr()), nitems, out_w, out_h,
-        _format_arg(tight), ctypes.c_void_p(d_out.data_ptr()), cap,
-        ctypes.c_void_p(d_len.data_ptr()), ctypes.c_void_p(scratch.data_ptr()),
-        ctypes.c_void_p(d_result.data_ptr()), _stream_handle(stream))
-    if rc != 0:
-        raise JpegError(rc, "jpegr_select_device")
+    d_result = _buffer(d_result, 3, torch.int64, dev)
+    scratch = _buffer(scratch, select_scratch_bytes(nitems, out_w, out_h), torch.uint8, dev,
+                      "scratch smaller than select_scratch_bytes(nitems, out_w, out_h)", floor=16)
+    _call("jpegr_select_device", d_stream, in_len, w, h, nimg, d_offsets, d_items, nitems, out_w,
+          out_h, _format_arg(tight), d_out, cap, d_len, scratch, d_result, stream_arg(stream))
     return d_out, d_len, d_result
 
 
@@ -555,9 +492,7 @@ def concat_streams(streams):
         raise ValueError("no streams")
     heads = []
     for d in streams:
-        if d.numel() < 16:
-            raise JpegError(-1, "concat_streams: shorter than a header")
-        heads.append(stream_format(d[:16].cpu().numpy().tobytes()))
+        heads.append(_open_stream(d, "concat_streams"))
     w, h, _, tight = heads[0]
     if any((hw, hh, ht) != (w, h, tight) for hw, hh, _, ht in heads):
         raise JpegError(-1, "concat_streams: the streams differ in w, h or format")
@@ -589,16 +524,13 @@ class StreamReader:
     header or index is inconsistent."""
 
     def __init__(self, d_stream):
-        if d_stream.numel() < 16:
-            raise JpegError(-1, "StreamReader: shorter than a header")
+        self.w, self.h, self.nimg, self.tight = _open_stream(d_stream, "StreamReader")
         self.d_stream = d_stream
         self.length = d_stream.numel()
-        self.w, self.h, self.nimg, self.tight = stream_format(d_stream[:16].cpu().numpy().tobytes())
         self.d_offsets, d_result = stream_index_device(d_stream, self.length, self.w, self.h,
                                                        self.nimg)
-        verdict = int(d_result[1].item())
-        if verdict != -1:
-            raise JpegError(-1, f"StreamReader: inconsistent stream (verdict {verdict})")
+        # the index call has no third word: only the verdict is read back
+        _raise_on_verdict("StreamReader", (None, int(d_result[1].item()), 0))
 
     def crop(self, image, x, y, w, h):
         """Pixels [x, x + w) x [y, y + h) of image `image`: a uint8 tensor (h, w, 4)."""
@@ -670,7 +602,7 @@ class StreamReader:
 
 
 def stream_encode_scratch_bytes(ntiles, cap):
-    return int(_lib.lib().jpegr_stream_encode_scratch_bytes(ntiles, cap))
+    return int(_lib.call("jpegr_stream_encode_scratch_bytes", ntiles, cap))
 
 
 def encode_stream_device(d_coef, w, h, nimg=1, tight=False, d_out=None, d_len=None, d_result=None,
@@ -686,27 +618,18 @@ def encode_stream_device(d_coef, w, h, nimg=1, tight=False, d_out=None, d_len=No
     Asynchronous: no read-back."""
     import torch
     nt = nimg * tiles(w, h)
-    if d_coef.numel() * d_coef.element_size() < nt * 256:
-        raise ValueError("d_coef smaller than ntiles * 128 int16")
     dev = d_coef.device
+    _buffer(d_coef, nt * 128, torch.int16, dev, "d_coef smaller than ntiles * 128 int16",
+            in_bytes=True)
     if d_out is None:
         d_out = torch.empty(pack_bound(w, h, nimg), dtype=torch.uint8, device=dev)
     if d_len is None:
         d_len = torch.zeros(1, dtype=torch.int64, device=dev)
-    if d_result is None:
-        d_result = torch.empty(2, dtype=torch.int64, device=dev)
-    need = stream_encode_scratch_bytes(nt, d_out.numel())
-    if scratch is None:
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif scratch.numel() < need:
-        raise ValueError("scratch smaller than stream_encode_scratch_bytes(ntiles, cap)")
-    rc = _lib.lib().jpegr_stream_encode_device(
-        ctypes.c_void_p(d_coef.data_ptr()), w, h, nimg, STREAM_JPT1 if tight else STREAM_JPR1,
-        ctypes.c_void_p(d_out.data_ptr()), d_out.numel(), ctypes.c_void_p(d_len.data_ptr()),
-        ctypes.c_void_p(scratch.data_ptr()), ctypes.c_void_p(d_result.data_ptr()),
-        _stream_handle(stream))
-    if rc != 0:
-        raise JpegError(rc, "jpegr_stream_encode_device")
+    d_result = _buffer(d_result, 2, torch.int64, dev)
+    scratch = _buffer(scratch, stream_encode_scratch_bytes(nt, d_out.numel()), torch.uint8, dev,
+                      "scratch smaller than stream_encode_scratch_bytes(ntiles, cap)")
+    _call("jpegr_stream_encode_device", d_coef, w, h, nimg, STREAM_JPT1 if tight else STREAM_JPR1,
+          d_out, d_out.numel(), d_len, scratch, d_result, stream_arg(stream))
     return d_out, d_len, d_result
 
 
@@ -761,16 +684,11 @@ def decompress_device(d_stream):
     jpegr_reconstruct_device).  Raises JpegError on an inconsistent stream
     (d_result[1] != ~0) or a malformed entropy stream (status[1] != 0)."""
     import torch
-    if d_stream.numel() < 16:
-        raise JpegError(-1, "decompress_device: shorter than a header")
-    w, h, nimg = stream_info(d_stream[:16].cpu().numpy().tobytes())
+    w, h, nimg, _ = _open_stream(d_stream, "decompress_device", slots=True)
     ent, d_result = unpack_device(d_stream, d_stream.numel(), w, h, nimg)
     d_coef = torch.empty(nimg * coef_count(w, h), dtype=torch.int16, device=d_stream.device)
     ent.decode(d_coef)
     out = reconstruct_device(d_coef, w, h, nimg)
-    if int(d_result[1].item()) != -1:
-        raise JpegError(-1, f"decompress_device: inconsistent stream (verdict "
-                            f"{int(d_result[1].item())})")
-    if int(ent.status[1].item()) != 0:
-        raise JpegError(-1, "decompress_device: malformed entropy stream")
+    # the slot decoder counts its rejected streams in the Entropy's status, not in d_result
+    _raise_on_verdict("decompress_device", (None, int(d_result[1].item()), int(ent.status[1].item())))
     return out, w, h, nimg

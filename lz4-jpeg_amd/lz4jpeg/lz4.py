@@ -10,12 +10,13 @@ Errors follow the reference's exit paths as exceptions: an input shorter than
 Device memory and streams come from torch (plumbing only); the compute is the
 C ABI in include/lz4r.h.
 """
-import ctypes
+import functools
+from ctypes import byref, c_float, c_size_t, c_void_p
 
 import numpy as np
 
 from . import _lib
-from ._lib import Lz4Error, LZ4R_BLOCK, LZ4R_BLOCK_BOUND  # noqa: F401
+from ._lib import Lz4Error, LZ4R_BLOCK, LZ4R_BLOCK_BOUND, stream_arg  # noqa: F401
 
 BLOCK = LZ4R_BLOCK
 
@@ -30,34 +31,42 @@ def _raise(code, where):
     raise Lz4Error(code, where)
 
 
+_call = functools.partial(_lib.call, error=_raise)      # a nonzero return raises
+
+
 def nblocks(n):
     return (n + BLOCK - 1) // BLOCK
 
 
 def compress_bound(n):
-    return int(_lib.lib().lz4r_compress_bound(n))
+    return int(_lib.call("lz4r_compress_bound", n))
 
 
-def _stream_handle(stream=None):
+def _output(d_out, out_cap, device):
+    """The caller's d_out, or out_cap new bytes (one at the least)."""
+    if d_out is not None:
+        return d_out
     import torch
-    s = stream if stream is not None else torch.cuda.current_stream()
-    return ctypes.c_void_p(s.cuda_stream)
+    return torch.empty(max(out_cap, 1), dtype=torch.uint8, device=device)
+
+
+def _offsets_arg(d_offsets):
+    """Block offsets come as an int64 tensor or as the raw device pointer
+    Compressor.block_offsets_device() returns."""
+    return d_offsets if isinstance(d_offsets, int) else d_offsets.data_ptr()
 
 
 class Compressor:
     """Owns an lz4r context (device scratch) on the current device."""
 
     def __init__(self):
-        L = _lib.lib()
-        h = ctypes.c_void_p()
-        rc = L.lz4r_ctx_create(ctypes.byref(h))
-        if rc != 0:
-            _raise(rc, "lz4r_ctx_create")
+        h = c_void_p()
+        _call("lz4r_ctx_create", byref(h))
         self._h = h
 
     def close(self):
         if getattr(self, "_h", None):
-            _lib.lib().lz4r_ctx_destroy(self._h)
+            _lib.call("lz4r_ctx_destroy", self._h)
             self._h = None
 
     def __del__(self):
@@ -74,12 +83,9 @@ class Compressor:
         n = d_in.numel() if n is None else n
         if d_out is None:
             d_out = torch.empty(compress_bound(n), dtype=torch.uint8, device=d_in.device)
-        got = ctypes.c_size_t(0)
-        rc = _lib.lib().lz4r_compress_device(self._h, ctypes.c_void_p(d_in.data_ptr()), n,
-                                             ctypes.c_void_p(d_out.data_ptr()), d_out.numel(),
-                                             ctypes.byref(got), _stream_handle(stream))
-        if rc != 0:
-            _raise(rc, "lz4r_compress_device")
+        got = c_size_t(0)
+        _call("lz4r_compress_device", self._h, d_in, n, d_out, d_out.numel(), byref(got),
+              stream_arg(stream))
         return d_out, got.value
 
     def compress_async(self, d_in, n, d_out, d_len, stream=None, segment=False,
@@ -94,16 +100,11 @@ class Compressor:
         the single-GPU one)."""
         if segment and final_shard is None:
             raise ValueError("compress_async(segment=True) needs final_shard=True/False")
-        L = _lib.lib()
-        args = (self._h, ctypes.c_void_p(d_in.data_ptr()), n, ctypes.c_void_p(d_out.data_ptr()),
-                d_out.numel(), ctypes.c_void_p(d_len.data_ptr()))
+        args = (self._h, d_in, n, d_out, d_out.numel(), d_len)
         if segment:
-            rc = L.lz4r_compress_segment_async(*args, 1 if final_shard else 0,
-                                               _stream_handle(stream))
+            _call("lz4r_compress_segment_async", *args, 1 if final_shard else 0, stream_arg(stream))
         else:
-            rc = L.lz4r_compress_async(*args, _stream_handle(stream))
-        if rc != 0:
-            _raise(rc, "lz4r_compress_segment_async" if segment else "lz4r_compress_async")
+            _call("lz4r_compress_async", *args, stream_arg(stream))
 
     @staticmethod
     def async_length(d_len):
@@ -121,53 +122,42 @@ class Compressor:
         """numpy uint64 array: the last call's first `count` per-block output
         offsets (relative to the first block byte)."""
         out = np.empty(count, dtype=np.uint64)
-        rc = _lib.lib().lz4r_copy_block_offsets(self._h, out.ctypes.data_as(ctypes.c_void_p),
-                                                count, _stream_handle(stream))
-        if rc != 0:
-            _raise(rc, "lz4r_copy_block_offsets")
+        _call("lz4r_copy_block_offsets", self._h, out, count, stream_arg(stream))
         return out
 
     def block_offsets_device(self):
         """(device pointer, count) of the last call's per-block offsets, as the
         placement kernel wrote them (valid until the next call on this
         context); lz4r_block_offsets_device."""
-        ptr, cnt = ctypes.c_void_p(), ctypes.c_size_t(0)
-        rc = _lib.lib().lz4r_block_offsets_device(self._h, ctypes.byref(ptr), ctypes.byref(cnt))
-        if rc != 0:
-            _raise(rc, "lz4r_block_offsets_device")
+        ptr, cnt = c_void_p(), c_size_t(0)
+        _call("lz4r_block_offsets_device", self._h, byref(ptr), byref(cnt))
         return ptr.value, cnt.value
 
     def check(self, stream=None):
         """lz4r_check: synchronise and raise Lz4Error(-6) if the last call met
         a corrupt bucket head (compress_device and async_length check by
         themselves)."""
-        rc = _lib.lib().lz4r_check(self._h, _stream_handle(stream))
-        if rc != 0:
-            _raise(rc, "lz4r_check")
+        _call("lz4r_check", self._h, stream_arg(stream))
 
     def set_timing(self, enable=True):
         """Record HIP events on the launch stream around each call and its
         match-finder/parse kernel (see last_timing)."""
-        _lib.lib().lz4r_set_timing(self._h, 1 if enable else 0)
+        _lib.call("lz4r_set_timing", self._h, 1 if enable else 0)
 
     def last_timing(self):
         """(ms of the whole last call, ms of its lz4_analyze kernel)."""
-        a, b = ctypes.c_float(0), ctypes.c_float(0)
-        rc = _lib.lib().lz4r_last_timing(self._h, ctypes.byref(a), ctypes.byref(b))
-        if rc != 0:
-            _raise(rc, "lz4r_last_timing")
+        a, b = c_float(0), c_float(0)
+        _call("lz4r_last_timing", self._h, byref(a), byref(b))
         return a.value, b.value
 
     def timed_calls(self, max_calls=4096):
         """(ms of each call, ms of its lz4_tiles launches): two lists over the
         newest calls timed since set_timing(True), oldest first (waits for
         the newest; lz4r_timed_calls)."""
-        a = (ctypes.c_float * max_calls)()
-        b = (ctypes.c_float * max_calls)()
-        cnt = ctypes.c_size_t(0)
-        rc = _lib.lib().lz4r_timed_calls(self._h, max_calls, a, b, ctypes.byref(cnt))
-        if rc != 0:
-            _raise(rc, "lz4r_timed_calls")
+        a = (c_float * max_calls)()
+        b = (c_float * max_calls)()
+        cnt = c_size_t(0)
+        _call("lz4r_timed_calls", self._h, max_calls, a, b, byref(cnt))
         return list(a[:cnt.value]), list(b[:cnt.value])
 
     # -- host convenience -------------------------------------------------
@@ -191,11 +181,8 @@ def compress(data):
         raise InputTooSmall(_lib.LZ4R_ERR_TOO_SMALL, "lz4r_compress")
     cap = 1 + nblocks(n) * LZ4R_BLOCK_BOUND
     out = np.empty(cap, dtype=np.uint8)
-    got = ctypes.c_size_t(0)
-    rc = _lib.lib().lz4r_compress(buf.ctypes.data_as(ctypes.c_void_p), n,
-                                  out.ctypes.data_as(ctypes.c_void_p), cap, ctypes.byref(got))
-    if rc != 0:
-        _raise(rc, "lz4r_compress")
+    got = c_size_t(0)
+    _call("lz4r_compress", buf, n, out, cap, byref(got))
     return out[:got.value].tobytes()
 
 
@@ -207,11 +194,8 @@ def decompress(stream, cap=None):
     if cap is None:
         cap = (buf.size // 5 + 1) * BLOCK
     out = np.empty(max(cap, 1), dtype=np.uint8)
-    got = ctypes.c_size_t(0)
-    rc = _lib.lib().lz4r_decompress(buf.ctypes.data_as(ctypes.c_void_p), buf.size,
-                                    out.ctypes.data_as(ctypes.c_void_p), cap, ctypes.byref(got))
-    if rc != 0:
-        _raise(rc, "lz4r_decompress")
+    got = c_size_t(0)
+    _call("lz4r_decompress", buf, buf.size, out, cap, byref(got))
     return out[:got.value].tobytes()
 
 
@@ -224,28 +208,27 @@ def decompress_device(d_stream, length, d_offsets, nb, out_cap, d_out=None, stre
     (d_out, decoded_length); raises Lz4Error(-6) naming the first malformed
     block.  check=False skips the result read-back (no host sync) and
     returns (d_out, None)."""
-    import torch
-    if d_out is None:
-        d_out = torch.empty(max(out_cap, 1), dtype=torch.uint8, device=d_stream.device)
-    res = torch.empty(2, dtype=torch.int64, device=d_stream.device)
-    offs = d_offsets if isinstance(d_offsets, int) else d_offsets.data_ptr()
-    rc = _lib.lib().lz4r_decompress_device(
-        ctypes.c_void_p(d_stream.data_ptr()), length, ctypes.c_void_p(offs), nb,
-        ctypes.c_void_p(d_out.data_ptr()), out_cap, ctypes.c_void_p(res.data_ptr()),
-        _stream_handle(stream))
-    if rc != 0:
-        _raise(rc, "lz4r_decompress_device")
-    if not check:
-        return d_out, None
-    if stream is not None:
-        stream.synchronize()          # the result is written on `stream`, not torch's current one
-    n, bad = (int(x) for x in res.cpu().tolist())
-    if bad != -1:
-        raise Lz4Error(_lib.LZ4R_ERR_CORRUPT, f"lz4r_decompress_device: block {bad - 1}")
-    if n > out_cap:
+    d_out = _output(d_out, out_cap, d_stream.device)
+    n = _decode_blocks(d_stream, length, d_offsets, nb, d_out, out_cap, stream, check,
+                       "lz4r_decompress_device")
+    if check and n > out_cap:
         raise Lz4Error(_lib.LZ4R_ERR_CAPACITY,
                        f"lz4r_decompress_device: needs {n} bytes, capacity {out_cap}")
     return d_out, n
+
+
+def _decode_blocks(d_stream, length, d_offsets, nb, d_out, out_cap, stream, check, who):
+    """lz4r_decompress_device; with check, the decoded length, read back, or
+    Lz4Error(-6) "<who>: block <first malformed block>".  d_out None, for an
+    out_cap of 0: no output, but every block is checked and counted all the
+    same (the result words stand in for the output)."""
+    import torch
+    res = torch.empty(2, dtype=torch.int64, device=d_stream.device)
+    _call("lz4r_decompress_device", d_stream, length, _offsets_arg(d_offsets), nb,
+          res if d_out is None else d_out, out_cap, res, stream_arg(stream))
+    if not check:
+        return None
+    return _lib.batch_verdict(res, stream, Lz4Error, _lib.LZ4R_ERR_CORRUPT, f"{who}: block")
 
 
 def decompress_stream_device(d_stream, length, out_cap, d_out=None, stream=None):
@@ -253,15 +236,10 @@ def decompress_stream_device(d_stream, length, out_cap, d_out=None, stream=None)
     the block boundaries are found on the device, as LZ4_decode (LZ4.c:1038)
     needs only the stream.  Returns (d_out, decoded_length); raises
     Lz4Error(-6) on a malformed stream."""
-    import torch
-    if d_out is None:
-        d_out = torch.empty(max(out_cap, 1), dtype=torch.uint8, device=d_stream.device)
-    got = ctypes.c_size_t(0)
-    rc = _lib.lib().lz4r_decompress_stream_device(
-        ctypes.c_void_p(d_stream.data_ptr()), length, ctypes.c_void_p(d_out.data_ptr()), out_cap,
-        ctypes.byref(got), _stream_handle(stream))
-    if rc != 0:
-        _raise(rc, "lz4r_decompress_stream_device")
+    d_out = _output(d_out, out_cap, d_stream.device)
+    got = c_size_t(0)
+    _call("lz4r_decompress_stream_device", d_stream, length, d_out, out_cap, byref(got),
+          stream_arg(stream))
     return d_out, got.value
 
 
@@ -271,12 +249,8 @@ def decompress_stream(stream_bytes, cap=None):
     if cap is None:
         cap = (buf.size // 8 + 1) * BLOCK
     out = np.empty(max(cap, 1), dtype=np.uint8)
-    got = ctypes.c_size_t(0)
-    rc = _lib.lib().lz4r_decompress_stream(buf.ctypes.data_as(ctypes.c_void_p), buf.size,
-                                           out.ctypes.data_as(ctypes.c_void_p), cap,
-                                           ctypes.byref(got))
-    if rc != 0:
-        _raise(rc, "lz4r_decompress_stream")
+    got = c_size_t(0)
+    _call("lz4r_decompress_stream", buf, buf.size, out, cap, byref(got))
     return out[:got.value].tobytes()
 
 
@@ -291,21 +265,21 @@ def stream_index_device(d_stream, length, stream=None):
     cap = length // 64 + 64
     for _ in range(2):
         d_offs = torch.empty(cap, dtype=torch.int64, device=d_stream.device)
-        nb, n = ctypes.c_size_t(0), ctypes.c_size_t(0)
-        rc = _lib.lib().lz4r_stream_index_device(
-            ctypes.c_void_p(d_stream.data_ptr()), length, ctypes.c_void_p(d_offs.data_ptr()), cap,
-            ctypes.byref(nb), ctypes.byref(n), _stream_handle(stream))
+        nb, n = c_size_t(0), c_size_t(0)
+        # no raise by the call itself: too small a first guess is answered, not an error
+        rc = _lib.call("lz4r_stream_index_device", d_stream, length, d_offs, cap, byref(nb),
+                       byref(n), stream_arg(stream))
         if rc != _lib.LZ4R_ERR_CAPACITY:
             break
         cap = nb.value
-    if rc != 0:
+    if rc:
         _raise(rc, "lz4r_stream_index_device")
     return d_offs[:nb.value], nb.value, n.value
 
 
 def read_items(max_len):
     """Lanes a read occupies in a call with this max_len (lz4r_read_items)."""
-    return int(_lib.lib().lz4r_read_items(max_len))
+    return int(_lib.call("lz4r_read_items", max_len))
 
 
 def read_device(d_stream, length, d_offsets, nb, d_src, d_len, max_len, d_dst=None, d_out=None,
@@ -331,26 +305,16 @@ def read_device(d_stream, length, d_offsets, nb, d_src, d_len, max_len, d_dst=No
             out_cap = int((d_dst + d_len).max().item())
         else:
             out_cap = nreads * max_len
-    if d_out is None:
-        d_out = torch.empty(max(out_cap, 1), dtype=torch.uint8, device=d_stream.device)
+    d_out = _output(d_out, out_cap, d_stream.device)
     if nreads == 0:
         return d_out, d_dst, (0 if check else None)
     d_reads = torch.stack((d_src, d_len, d_dst), dim=1).contiguous()
     res = torch.empty(2, dtype=torch.int64, device=d_stream.device)
-    offs = d_offsets if isinstance(d_offsets, int) else d_offsets.data_ptr()
-    rc = _lib.lib().lz4r_read_device(
-        ctypes.c_void_p(d_stream.data_ptr()), length, ctypes.c_void_p(offs), nb,
-        ctypes.c_void_p(d_reads.data_ptr()), nreads, max_len, ctypes.c_void_p(d_out.data_ptr()),
-        out_cap, ctypes.c_void_p(res.data_ptr()), _stream_handle(stream))
-    if rc != 0:
-        _raise(rc, "lz4r_read_device")
+    _call("lz4r_read_device", d_stream, length, _offsets_arg(d_offsets), nb, d_reads, nreads, max_len,
+          d_out, out_cap, res, stream_arg(stream))
     if not check:
         return d_out, d_dst, None
-    if stream is not None:
-        stream.synchronize()          # the result is written on `stream`, not torch's current one
-    n, bad = (int(x) for x in res.cpu().tolist())
-    if bad != -1:
-        raise Lz4Error(_lib.LZ4R_ERR_CORRUPT, f"lz4r_read_device: read {bad - 1}")
+    n = _lib.batch_verdict(res, stream, Lz4Error, _lib.LZ4R_ERR_CORRUPT, "lz4r_read_device: read")
     return d_out, d_dst, n
 
 
@@ -369,19 +333,8 @@ class Reader:
         if self.decoded_length is None:
             # the block decoder with no room for output checks every block
             # and reports the decoded length
-            import torch
-            res = torch.empty(2, dtype=torch.int64, device=d_stream.device)
-            offs = d_offsets if isinstance(d_offsets, int) else d_offsets.data_ptr()
-            rc = _lib.lib().lz4r_decompress_device(
-                ctypes.c_void_p(d_stream.data_ptr()), self.length, ctypes.c_void_p(offs), self.nb,
-                ctypes.c_void_p(res.data_ptr()), 0, ctypes.c_void_p(res.data_ptr()),
-                _stream_handle())
-            if rc != 0:
-                _raise(rc, "lz4r_decompress_device")
-            n, bad = (int(x) for x in res.cpu().tolist())
-            if bad != -1:
-                raise Lz4Error(_lib.LZ4R_ERR_CORRUPT, f"Reader: block {bad - 1}")
-            self.decoded_length = n
+            self.decoded_length = _decode_blocks(d_stream, self.length, d_offsets, self.nb, None, 0,
+                                                 None, True, "Reader")
 
     def read(self, src, n):
         """Decoded bytes [src, src + n) as a uint8 tensor."""

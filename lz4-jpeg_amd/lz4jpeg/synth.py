@@ -11,12 +11,12 @@ The corpus source text (Output-Input/input/Metamorphosis.txt, 118,489 B) is
 committed as data under tests/golden/ so the GPU box never reads the
 reference tree.
 """
-import ctypes
 import os
 
 import numpy as np
 
 from . import _lib
+from ._lib import stream_arg
 
 _REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CORPUS_PATH = os.path.join(_REPO, "tests", "golden", "Metamorphosis.txt")
@@ -30,7 +30,7 @@ def corpus():
 def rand_rgba(w, h, seed=1):
     """(h, w, 4) uint8 from glibc rand() after srand(seed)."""
     out = np.empty((h, w, 4), dtype=np.uint8)
-    _lib.lib().lz4jpeg_rand_rgba(seed, w, h, out.ctypes.data_as(ctypes.c_void_p))
+    _lib.call("lz4jpeg_rand_rgba", seed, w, h, out)
     return out
 
 
@@ -40,9 +40,7 @@ def random_passages(total, length=30000, seed=1, first=0, src=None):
     src = corpus() if src is None else src
     s = np.frombuffer(src, dtype=np.uint8)
     out = np.empty(total, dtype=np.uint8)
-    got = _lib.lib().lz4jpeg_random_passages(s.ctypes.data_as(ctypes.c_void_p), s.size, seed,
-                                             length, first, total,
-                                             out.ctypes.data_as(ctypes.c_void_p))
+    got = _lib.call("lz4jpeg_random_passages", s, s.size, seed, length, first, total, out)
     if got != total:
         raise ValueError("random_passages: bad arguments")
     return out
@@ -52,15 +50,12 @@ def rand_rgba_stream(first_pixel, npix, seed=1):
     """(npix, 4) uint8: pixels [first_pixel, first_pixel + npix) of the
     rand() stream after srand(seed) (pixel i = outputs 3i, 3i+1, 3i+2)."""
     out = np.empty((npix, 4), dtype=np.uint8)
-    _lib.lib().lz4jpeg_rand_rgba_stream(seed, first_pixel, npix,
-                                        out.ctypes.data_as(ctypes.c_void_p))
+    _lib.call("lz4jpeg_rand_rgba_stream", seed, first_pixel, npix, out)
     return out
 
 
-def _stream_ptr(stream):
-    import torch
-    s = stream if stream is not None else torch.cuda.current_stream()
-    return ctypes.c_void_p(s.cuda_stream)
+def _error(code, where):
+    return RuntimeError(f"{where}: error {code}")
 
 
 def rand_rgba_device(d_out, first_pixel, npix, seed=1, stream=None):
@@ -68,11 +63,8 @@ def rand_rgba_device(d_out, first_pixel, npix, seed=1, stream=None):
     rand_rgba_stream(first_pixel, npix, seed) returns."""
     if d_out.numel() * d_out.element_size() < 4 * npix:
         raise ValueError("rand_rgba_device: output too small")
-    rc = _lib.lib().lz4jpeg_rand_rgba_device(seed, first_pixel, npix,
-                                             ctypes.c_void_p(d_out.data_ptr()),
-                                             _stream_ptr(stream))
-    if rc != 0:
-        raise RuntimeError(f"lz4jpeg_rand_rgba_device: error {rc}")
+    _lib.call("lz4jpeg_rand_rgba_device", seed, first_pixel, npix, d_out, stream_arg(stream),
+              error=_error)
     return d_out
 
 
@@ -83,10 +75,6 @@ def random_passages_device(d_out, total, length=30000, seed=1, first=0, src=None
     s = np.frombuffer(src, dtype=np.uint8)
     if d_out.numel() < total:
         raise ValueError("random_passages_device: output too small")
-    rc = _lib.lib().lz4jpeg_random_passages_device(s.ctypes.data_as(ctypes.c_void_p), s.size,
-                                                   seed, length, first, total,
-                                                   ctypes.c_void_p(d_out.data_ptr()),
-                                                   _stream_ptr(stream))
-    if rc != 0:
-        raise RuntimeError(f"lz4jpeg_random_passages_device: error {rc}")
+    _lib.call("lz4jpeg_random_passages_device", s, s.size, seed, length, first, total, d_out,
+              stream_arg(stream), error=_error)
     return d_out

@@ -41,6 +41,23 @@ def to_dev(a, dtype):
     return torch.from_numpy(np.ascontiguousarray(a, dtype).reshape(-1).view(np.uint8).copy()).cuda()
 
 
+def dev_bytes(data):
+    import torch
+    return torch.from_numpy(np.frombuffer(bytes(data), np.uint8).copy()).cuda()
+
+
+def dev_u64(values):
+    import torch
+    return torch.from_numpy(np.array([int(v) & U64 for v in values], np.uint64).view(np.int64)).cuda()
+
+
+def host_offsets(data, dims):
+    """ntiles + 1 offsets: the cumulative sum of the u16 index from 16 + 2 ntiles."""
+    nt = J.ntiles_of(*dims)
+    sizes = np.frombuffer(data[16:16 + 2 * nt], "<u2").astype(np.uint64)
+    return np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64) + np.uint64(16 + 2 * nt)
+
+
 def coef_dev(coef):
     import torch
     return torch.from_numpy(np.array(coef, np.int16).reshape(-1)).cuda()

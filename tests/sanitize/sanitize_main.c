@@ -2,7 +2,7 @@
  * sanitize_main.c -- TEST INFRASTRUCTURE ONLY ("CPU
  * restatement under ASan/UBSan").  Built by `make sanitize` with
  * -fsanitize=address,undefined -fno-sanitize-recover=all together with the
- * host C of the product (lz4r_decode.c, png_io.c, synth.c) and the oracle
+ * host C of the product (lz4r_decode.c, png_io.c, read_file.c, synth.c) and the oracle
  * restatements (oracle/*.c); run by tests/test_sanitize.py.  Exercises:
  *   - the oracle LZ4 encoder on the golden inputs + adversarial blocks, and
  *     the product's exact host decoder (lz4r_decompress) round trip, plus
@@ -51,18 +51,6 @@ static int fails = 0;
       ++fails;                                                          \
     }                                                                   \
   } while (0)
-
-static uint8_t *read_file(const char *path, size_t *n) {
-  FILE *f = fopen(path, "rb");
-  if (!f) return NULL;
-  fseek(f, 0, SEEK_END);
-  long sz = ftell(f);
-  fseek(f, 0, SEEK_SET);
-  uint8_t *b = malloc((size_t)sz);
-  *n = fread(b, 1, (size_t)sz, f);
-  fclose(f);
-  return b;
-}
 
 /* compress with the oracle, decode with the product's host decoder; also
  * every truncation of the stream's tail and a few corruptions must not
@@ -116,7 +104,8 @@ static void compat_block(const uint8_t *src, size_t n, const char *tmp) {
   write_output(&frame, f);
   fclose(f);
   size_t got = 0;
-  uint8_t *bytes = read_file(path, &got);
+  uint8_t *bytes = NULL;
+  CHECK(lzj_read_file(path, &bytes, &got) == 0);
   uint8_t *want = malloc(1 + 3 + n + 8 * (n / 4 + 8) + 1024);
   want[0] = 1;
   const size_t wl = 1 + lz4o_encode_block(blk, n, want + 1);
@@ -134,7 +123,8 @@ int main(int argc, char **argv) {
   /* ---- LZ4 ---- */
   snprintf(path, sizeof path, "%s/Metamorphosis.txt", golden);
   size_t mn = 0;
-  uint8_t *meta = read_file(path, &mn);
+  uint8_t *meta = NULL;
+  (void)lzj_read_file(path, &meta, &mn);
   CHECK(meta && mn > 100000);
   if (meta) {
     lz4_roundtrip(meta, 300);
@@ -208,7 +198,11 @@ int main(int argc, char **argv) {
     CHECK(rw == w && rh == h && back && memcmp(back, img, (size_t)w * h * 4) == 0);
     free(back);
     size_t pn = 0;
-    uint8_t *raw = read_file(path, &pn);
+    uint8_t *raw = NULL;
+    CHECK(lzj_read_file(path, &raw, &pn) == 0);
+    size_t none = 1;
+    snprintf(path, sizeof path, "%s/sanitize_no_such_file", tmp);
+    CHECK(lzj_read_file(path, &back, &none) == LZJ_FILE_IO && !back && none == 0);
     snprintf(path, sizeof path, "%s/sanitize_cut.png", tmp);
     FILE *f = fopen(path, "wb");
     fwrite(raw, 1, pn / 2, f);

@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 
 import jpr_crop_model as M
-from jpr_gpu_lib import FILL, GUARD, U64, encoded_jpr, image, jpr_mutations
+from jpr_gpu_lib import (FILL, GUARD, U64, dev_bytes, dev_u64, encoded_jpr, host_offsets, image,
+                         jpr_mutations)
 
 pytestmark = pytest.mark.gpu
 
@@ -38,23 +39,6 @@ def full_of(d_stream):
     from lz4jpeg import jpeg
     full, w, h, nimg = jpeg.decompress_images_device(d_stream)
     return full.cpu().numpy().reshape(nimg, h, w, 4)
-
-
-def host_offsets(data, dims):
-    """ntiles + 1 offsets: the cumulative sum of the u16 index from 16 + 2 ntiles."""
-    nt = dims[2] * ((dims[0] + 7) // 8) * ((dims[1] + 7) // 8)
-    sizes = np.frombuffer(data[16:16 + 2 * nt], "<u2").astype(np.uint64)
-    return np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64) + np.uint64(16 + 2 * nt)
-
-
-def dev_bytes(data):
-    import torch
-    return torch.from_numpy(np.frombuffer(bytes(data), np.uint8).copy()).cuda()
-
-
-def dev_u64(values):
-    import torch
-    return torch.from_numpy(np.array([int(v) & U64 for v in values], np.uint64).view(np.int64)).cuda()
 
 
 def gpu_index(data, in_len, dims):

@@ -13,7 +13,7 @@ import jpr_format as J
 import jpr_select_model as M
 import jpt_format as T
 import jpt_inputs as I
-from jpr_gpu_lib import FILL, GUARD, U64, crafted, image
+from jpr_gpu_lib import FILL, GUARD, U64, crafted, dev_bytes, dev_u64, image
 
 pytestmark = pytest.mark.gpu
 
@@ -23,16 +23,6 @@ GARBAGE = 0x5A5A5A5A5A5A5A5A
 
 
 # ---- streams and drivers ----------------------------------------------------------
-
-def dev_bytes(data):
-    import torch
-    return torch.from_numpy(np.frombuffer(bytes(data), np.uint8).copy()).cuda()
-
-
-def dev_u64(values):
-    import torch
-    return torch.from_numpy(np.array([int(v) & U64 for v in values], np.uint64).view(np.int64)).cuda()
-
 
 def compress(imgs, tight):
     """compress_device of images [n, h, w, 4], as bytes."""

@@ -13,8 +13,8 @@ import pytest
 
 import jpr_crop_model as CM
 import jpr_thumb_model as M
-from jpr_gpu_lib import (FILL, GUARD, U64, coef_dev, encoded_jpr, gpu_decode, image,
-                         jpr_mutations, pack_scratch, random_coef)
+from jpr_gpu_lib import (FILL, GUARD, U64, coef_dev, dev_bytes, dev_u64, encoded_jpr, gpu_decode,
+                         host_offsets, image, jpr_mutations, pack_scratch, random_coef)
 
 pytestmark = pytest.mark.gpu
 
@@ -24,24 +24,8 @@ GARBAGE = 0x5A5A5A5A5A5A5A5A
 
 # ---- drivers ------------------------------------------------------------------------
 
-def dev_bytes(data):
-    import torch
-    return torch.from_numpy(np.frombuffer(bytes(data), np.uint8).copy()).cuda()
-
-
-def dev_u64(values):
-    import torch
-    return torch.from_numpy(np.array([int(v) & U64 for v in values], np.uint64).view(np.int64)).cuda()
-
-
 def tiles_of(dims):
     return ((dims[0] + 7) // 8) * ((dims[1] + 7) // 8)
-
-
-def host_offsets(data, dims):
-    nt = dims[2] * tiles_of(dims)
-    sizes = np.frombuffer(data[16:16 + 2 * nt], "<u2").astype(np.uint64)
-    return np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64) + np.uint64(16 + 2 * nt)
 
 
 def stream_from_coef(coef, dims, tight, direct):

@@ -422,6 +422,60 @@ int jpegr_crop_device(const void *d_in, size_t in_len, int w, int h, int nimg,
                       int max_w, int max_h, void *d_out, size_t out_cap,
                       void *d_scratch, void *d_result, void *stream);
 
+/* jpegr_crop_tensor_device: jpegr_crop_device's rectangles delivered as what a
+ * model reads -- three channels, planar or interleaved, in its dtype,
+ * normalised, optionally mirrored -- in the same three launches.  d_rects
+ * (jpegr_rect as above), d_tile_offsets (untrusted), the K =
+ * jpegr_crop_items(max_w, max_h) mapping, the scratch
+ * (jpegr_crop_scratch_bytes), the three result words and the good / bad /
+ * empty rules are jpegr_crop_device's, with one difference: dst and out_cap
+ * count ELEMENTS of the output dtype from d_out (16-B aligned).  A rectangle
+ * occupies 3 w h elements; it is bad when dst + 3 w h > out_cap (no sum
+ * wraps); no dst is misaligned, an element offset being element-aligned.  Wide
+ * stores are taken only where the address allows: odd w, or a dst that is not
+ * a multiple of 16 B, is inside the contract.
+ * Values: channel c (0 R, 1 G, 2 B; alpha dropped) of crop pixel (i, j) is the
+ * byte v that jpegr_crop_device delivers there.  JPEGR_DTYPE_U8: the element
+ * is v, scale3 and bias3 are ignored.  Otherwise
+ *   f = fl32(fl32((float)v * scale3[c]) + bias3[c]),
+ * two fp32 operations, each rounded, never fused: bit for bit what
+ * x.float().mul(scale).add(bias) gives.  F32 stores f; F16 and BF16 store f
+ * rounded to nearest-even; f32 and f16 subnormals are kept.
+ * scale3, bias3: HOST pointers to three floats, read during the call and
+ * passed as kernel arguments (capturable); NULL: 1.0 and 0.0.
+ * d_flip: NULL, or nrects bytes on the device (any alignment, read inside
+ * [0, nrects) only); a nonzero byte mirrors that crop horizontally: output
+ * column j holds crop column w - 1 - j.
+ * Placement: JPEGR_LAYOUT_CHW: plane c of a crop starts at dst + c w h, rows
+ * of w elements; JPEGR_LAYOUT_HWC: pixel (i, j) is at dst + 3 (i w + j).
+ * Equal-sized crops at dst = r * 3 w h form an [n, 3, h, w] or [n, h, w, 3]
+ * tensor.
+ * Good rectangles are delivered exactly, whatever the bad ones do.  No read
+ * leaves d_in[0, in_len), d_tile_offsets[0, ntiles], d_rects[0, nrects) and
+ * d_flip[0, nrects); no write leaves d_result, the scratch and each good
+ * rectangle's own 3 w h elements within out_cap.  A rectangle bad on its own
+ * fields or on the header writes nothing; one that fails inside a tile may
+ * leave unspecified values in its own elements.  Overlapping destination
+ * ranges hold unspecified values.
+ * Asynchronous on `stream`, no host read-back, nothing kept on the host
+ * (capturable and replayable).  JPEGR_ERR_ARG before any HIP call: everything
+ * jpegr_crop_device rejects, with d_out 16-B aligned in place of 4-B (d_flip,
+ * scale3 and bias3 may be NULL); a dtype or layout that is none of the values
+ * below; a scale or bias that is not finite. */
+#define JPEGR_DTYPE_U8   0
+#define JPEGR_DTYPE_F32  1
+#define JPEGR_DTYPE_F16  2
+#define JPEGR_DTYPE_BF16 3
+#define JPEGR_LAYOUT_CHW 0   /* [3][h][w] */
+#define JPEGR_LAYOUT_HWC 1   /* [h][w][3] */
+
+int jpegr_crop_tensor_device(const void *d_in, size_t in_len, int w, int h, int nimg,
+                             const void *d_tile_offsets, const void *d_rects, size_t nrects,
+                             const void *d_flip, int max_w, int max_h,
+                             int dtype, int layout, const float *scale3, const float *bias3,
+                             void *d_out, size_t out_cap,
+                             void *d_scratch, void *d_result, void *stream);
+
 /* Thumbnails: images [image0, image0 + nimage) of a JPR1 or JPT1 stream at 1/8
  * scale, one RGBA8 pixel per tile, from the tiles' DC terms alone.  With
  * gw = ceil(w / 8) and gh = ceil(h / 8), pixel (tx, ty) of an image's

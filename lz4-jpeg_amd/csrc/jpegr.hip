@@ -4,7 +4,8 @@
 //                  quantisation -> zigzag -> int16 (jpeg_strip_kernel)
 //   jpegr_recon.h  the reconstruction: dequantisation, IDCT, YCbCr -> RGBA, of
 //                  whole images (jpeg_recon_kernel) and of rectangles
-//                  (jpeg_crop_recon_kernel)
+//                  (jpeg_crop_recon_kernel: RGBA8 rows; jpeg_crop_tensor_kernel:
+//                  three channels as a tensor's elements)
 // This file holds what they share -- the strip sizes, the LDS strides, the
 // tables -- and the host side: the launches and the C ABI.
 //
@@ -104,6 +105,49 @@ int jpegr_crop_recon_launch(const int16_t *d_coef, const uint32_t *d_status,
     hipLaunchKernelGGL(jpeg_crop_recon_kernel, dim3((unsigned)(nwg - b < step ? nwg - b : step)),
                        dim3(kThreads), 0, st, d_coef, d_status, d_rects, nrects, b, gwm, ghm, strips,
                        d_out, d_result);
+  return hipGetLastError() == hipSuccess ? JPEGR_OK : JPEGR_ERR_HIP;
+}
+
+namespace {
+
+using CropTensorKernel = void (*)(const int16_t *, const uint32_t *, const jpegr_rect *, size_t, size_t,
+                                  uint32_t, uint32_t, uint32_t, const uint8_t *, TensorNorm, void *,
+                                  uint64_t *);
+
+// jpeg_crop_tensor_kernel<dtype, layout>, one instance per pair
+CropTensorKernel crop_tensor_kernel_of(int dtype, int layout) {
+  static const CropTensorKernel k[4][2] = {
+      {jpeg_crop_tensor_kernel<JPEGR_DTYPE_U8, JPEGR_LAYOUT_CHW>,
+       jpeg_crop_tensor_kernel<JPEGR_DTYPE_U8, JPEGR_LAYOUT_HWC>},
+      {jpeg_crop_tensor_kernel<JPEGR_DTYPE_F32, JPEGR_LAYOUT_CHW>,
+       jpeg_crop_tensor_kernel<JPEGR_DTYPE_F32, JPEGR_LAYOUT_HWC>},
+      {jpeg_crop_tensor_kernel<JPEGR_DTYPE_F16, JPEGR_LAYOUT_CHW>,
+       jpeg_crop_tensor_kernel<JPEGR_DTYPE_F16, JPEGR_LAYOUT_HWC>},
+      {jpeg_crop_tensor_kernel<JPEGR_DTYPE_BF16, JPEGR_LAYOUT_CHW>,
+       jpeg_crop_tensor_kernel<JPEGR_DTYPE_BF16, JPEGR_LAYOUT_HWC>}};
+  return k[dtype][layout];
+}
+
+}  // namespace
+
+int jpegr_crop_tensor_launch(const int16_t *d_coef, const uint32_t *d_status,
+                             const jpegr_rect *d_rects, size_t nrects, int max_w, int max_h,
+                             const uint8_t *d_flip, int dtype, int layout, const float *scale3,
+                             const float *bias3, void *d_out, uint64_t *d_result, hipStream_t st) {
+  const uint32_t gwm = jpegr_crop::crop_span((uint32_t)max_w), ghm = jpegr_crop::crop_span((uint32_t)max_h);
+  const uint32_t strips = (gwm + kTiles - 1) / kTiles;
+  TensorNorm nm;
+  for (int c = 0; c < 3; ++c) {
+    nm.s[c] = scale3 ? scale3[c] : 1.0f;
+    nm.b[c] = bias3 ? bias3[c] : 0.0f;
+  }
+  const CropTensorKernel kernel = crop_tensor_kernel_of(dtype, layout);
+  // at most 2^22 workgroups a launch, as jpegr_crop_recon_launch
+  const size_t nwg = nrects * ghm * strips, step = (size_t)1 << 22;
+  for (size_t b = 0; b < nwg; b += step)
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(nwg - b < step ? nwg - b : step)), dim3(kThreads), 0, st,
+                       d_coef, d_status, d_rects, nrects, b, gwm, ghm, strips, d_flip, nm, d_out,
+                       d_result);
   return hipGetLastError() == hipSuccess ? JPEGR_OK : JPEGR_ERR_HIP;
 }
 

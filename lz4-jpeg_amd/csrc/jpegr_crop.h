@@ -48,3 +48,11 @@ __device__ __forceinline__ Grid grid_of(const jpegr_rect &rc) {
 __attribute__((visibility("hidden"))) int jpegr_crop_recon_launch(
     const int16_t *d_coef, const uint32_t *d_status, const jpegr_rect *d_rects, size_t nrects,
     int max_w, int max_h, uint8_t *d_out, uint64_t *d_result, hipStream_t st);
+
+// The same for jpegr_crop_tensor_device (jpeg_crop_tensor_kernel): d_flip NULL
+// or a byte per rectangle, scale3 and bias3 three floats each on the host, read
+// here and passed by value; dtype and layout are the header's, already checked.
+__attribute__((visibility("hidden"))) int jpegr_crop_tensor_launch(
+    const int16_t *d_coef, const uint32_t *d_status, const jpegr_rect *d_rects, size_t nrects,
+    int max_w, int max_h, const uint8_t *d_flip, int dtype, int layout, const float *scale3,
+    const float *bias3, void *d_out, uint64_t *d_result, hipStream_t st);

@@ -2,7 +2,8 @@
 // defines the strip size, the LDS strides and the tables before including
 // this): one text of the dequantisation, the IDCT and the pixel for whole
 // images (jpeg_recon_kernel) and for rectangles (jpeg_crop_recon_kernel, the
-// second half of jpegr_crop_device: jpegr_crop.h).
+// second half of jpegr_crop_device: jpegr_crop.h; jpeg_crop_tensor_kernel, that
+// of jpegr_crop_tensor_device, which delivers elements of a tensor).
 #pragma once
 
 #pragma clang fp contract(off)
@@ -267,6 +268,216 @@ __global__ __launch_bounds__(kThreads) void jpeg_crop_recon_kernel(
       // pixel k is column xo + k of the rectangle, stored only where that is inside
       const int64_t xo = (int64_t)(sx0 + (uint64_t)lx0) - (int64_t)rc.x;
       store_px4(dst + xo * 4, px, okp);
+    }
+  }
+}
+
+// ---- crops as tensors (jpegr_crop_tensor_device, include/jpegr.h) -------------
+// The element of one channel byte v: U8 the byte; otherwise
+// f = fl32(fl32((float)v * s) + b), two fp32 operations each rounded (no
+// contraction in this file), stored as fp32 bits, or rounded to nearest-even
+// to f16 (the hardware conversion, subnormals kept) or to bf16 (on the fp32
+// bits; f is never a NaN: v and s, b are finite).
+template <int DT>
+struct TensorElem {
+  using type = uint16_t;
+};
+template <>
+struct TensorElem<JPEGR_DTYPE_U8> {
+  using type = uint8_t;
+};
+template <>
+struct TensorElem<JPEGR_DTYPE_F32> {
+  using type = uint32_t;
+};
+
+template <int DT>
+__device__ __forceinline__ typename TensorElem<DT>::type tensor_elem(uint32_t v, float s, float b) {
+  if constexpr (DT == JPEGR_DTYPE_U8) {
+    return (uint8_t)v;
+  } else {
+    const float p = (float)v * s;
+    const float f = p + b;
+    if constexpr (DT == JPEGR_DTYPE_F32) {
+      return __float_as_uint(f);
+    } else if constexpr (DT == JPEGR_DTYPE_F16) {
+      return __builtin_bit_cast(uint16_t, (_Float16)f);
+    } else {
+      const uint32_t u = __float_as_uint(f);
+      return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+    }
+  }
+}
+
+// B bytes (dwords wd) to p, whose address is A0 mod 16 (A0 a multiple of 4):
+// from the front, the widest of 16, 8 and 4 B that the address there and the
+// rest allow -- 48 B at 8 mod 16 go as 8, 16, 16, 8.
+template <int A0, int B, int OFF = 0>
+__device__ __forceinline__ void store_words(uint8_t *p, const uint32_t *wd) {
+  if constexpr (OFF < B) {
+    constexpr int pos = (A0 + OFF) & 15, rem = B - OFF;
+    constexpr int n = (pos == 0 && rem >= 16) ? 16 : ((pos & 7) == 0 && rem >= 8) ? 8 : 4;
+    if constexpr (n == 16)
+      *reinterpret_cast<uint4 *>(p + OFF) =
+          make_uint4(wd[OFF / 4], wd[OFF / 4 + 1], wd[OFF / 4 + 2], wd[OFF / 4 + 3]);
+    else if constexpr (n == 8)
+      *reinterpret_cast<uint2 *>(p + OFF) = make_uint2(wd[OFF / 4], wd[OFF / 4 + 1]);
+    else
+      *reinterpret_cast<uint32_t *>(p + OFF) = wd[OFF / 4];
+    store_words<A0, B, OFF + n>(p, wd);
+  }
+}
+
+// A thread's run: 4 pixels of C elements each (C = 1: a plane's; C = 3:
+// interleaved), pixel m at q + C m where ok[m].  All four there and q
+// dword-aligned: wide stores by the address (store_words); else the elements
+// of the pixels that are there, one by one.
+template <typename E, int C>
+__device__ __forceinline__ void store_run(E *q, const E (&e)[4 * C], const bool (&ok)[4]) {
+  constexpr int B = 4 * C * (int)sizeof(E);
+  const uint32_t a = (uint32_t)(uintptr_t)q & 15u;
+  if (ok[0] && ok[3] && (a & 3u) == 0) {
+    uint32_t wd[B / 4];
+#pragma unroll
+    for (int i = 0; i < B / 4; ++i) {
+      if constexpr (sizeof(E) == 4) {
+        wd[i] = e[i];
+      } else if constexpr (sizeof(E) == 2) {
+        wd[i] = (uint32_t)e[2 * i] | ((uint32_t)e[2 * i + 1] << 16);
+      } else {
+        wd[i] = (uint32_t)e[4 * i] | ((uint32_t)e[4 * i + 1] << 8) | ((uint32_t)e[4 * i + 2] << 16) |
+                ((uint32_t)e[4 * i + 3] << 24);
+      }
+      // the packed word, opaque from here on: seen through, the f16 run was
+      // taken apart again and stored as short, dword at + 2, short
+      if constexpr (sizeof(E) < 4) asm volatile("" : "+v"(wd[i]));
+    }
+    uint8_t *const p = reinterpret_cast<uint8_t *>(q);
+    if (a == 0) store_words<0, B>(p, wd);
+    else if (a == 8) store_words<8, B>(p, wd);
+    else if (a == 4) store_words<4, B>(p, wd);
+    else store_words<12, B>(p, wd);
+  } else {
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+      if (ok[m]) {
+#pragma unroll
+        for (int ch = 0; ch < C; ++ch) q[C * m + ch] = e[C * m + ch];
+      }
+  }
+}
+
+// scale3 and bias3 of the call, by value: kernel arguments, so a captured
+// launch keeps them
+struct TensorNorm {
+  float s[3], b[3];
+};
+
+// jpeg_crop_recon_kernel's workgroup, phases 1 and 2 and verdict counting, with
+// another phase 3: the pixel's R, G and B become elements of DT (tensor_elem),
+// placed by LAY -- CHW: plane ch of the crop at dst + ch w h, rows of w
+// elements; HWC: pixel (i, j) at dst + 3 (i w + j), dst in elements -- and
+// mirrored where flip[ri] is not 0: output column j holds crop column
+// w - 1 - j.  A thread's four pixels are one run in every case (store_run):
+// columns xo .. xo + 3 of the crop, or, mirrored, the same four in reverse
+// order at columns w - 4 - xo .. w - 1 - xo.  Consecutive lanes hold
+// consecutive runs, so the stores of a wave's row are one contiguous range
+// from registers, in HWC too.
+template <int DT, int LAY>
+__global__ __launch_bounds__(kThreads) void jpeg_crop_tensor_kernel(
+    const int16_t *__restrict__ coef, const uint32_t *__restrict__ status,
+    const jpegr_rect *__restrict__ rects, size_t nrects, size_t wg_base, uint32_t gwm,
+    uint32_t ghm, uint32_t strips, const uint8_t *__restrict__ flip, TensorNorm nm,
+    void *__restrict__ out, uint64_t *__restrict__ result) {
+  using E = typename TensorElem<DT>::type;
+  __shared__ double yac[kTiles * kYStride];
+  __shared__ double crac[kTiles * kCStride];
+  __shared__ double cbac[kTiles * kCStride];
+  __shared__ uint8_t ys[kTiles * 64], crs[kTiles * 32], cbs[kTiles * 32];
+
+  const size_t wg = wg_base + blockIdx.x;
+  const size_t per = (size_t)ghm * strips;
+  const size_t ri = wg / per;
+  if (ri >= nrects) return;
+  const uint32_t rem = (uint32_t)(wg - ri * per);
+  const uint32_t cy = rem / strips, bc0 = (rem - cy * strips) * kTiles;
+  const int t = threadIdx.x;
+  const uint32_t stat = status[ri];
+  if (rem == 0 && t == 0) {
+    if (stat == jpegr_crop::kBad)
+      atomicMin(reinterpret_cast<unsigned long long *>(result + 1), 1ull + (unsigned long long)ri);
+    else
+      atomicAdd(reinterpret_cast<unsigned long long *>(result), 1ull);
+  }
+  if (stat != jpegr_crop::kGood) return;
+  const jpegr_rect rc = rects[ri];
+  const jpegr_crop::Grid g = jpegr_crop::grid_of(rc);
+  if (cy >= g.gh || bc0 >= g.gw) return;
+  const int ntiles = (int)min((uint32_t)kTiles, g.gw - bc0);
+  const bool mirror = flip != nullptr && flip[ri] != 0;           // inside [0, nrects)
+
+  recon_dequant(coef + ((ri * gwm * ghm) + (size_t)cy * g.gw + bc0) * 128, ntiles, t, yac, crac, cbac);
+  __syncthreads();
+  recon_idct(t, yac, crac, cbac, ys, crs, cbs);
+  __syncthreads();
+
+  // ---- phase 3: the pixels inside the rectangle, as elements --------------------
+  {
+    const int r = t >> 5, c = t & 31;
+    const uint64_t row = ((uint64_t)(g.ty0 + cy) << 3) + (uint64_t)r;     // image row
+    if (row < rc.y || row >= rc.y + rc.h) return;
+    const uint64_t plane = rc.w * rc.h;                                   // w, h < 2^31
+    const uint64_t row0 = rc.dst + (row - rc.y) * rc.w * (LAY == JPEGR_LAYOUT_CHW ? 1u : 3u);
+    const uint64_t sx0 = (uint64_t)(g.tx0 + bc0) << 3;                    // the strip's first column
+    E *const base = static_cast<E *>(out);
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      const int lx0 = half * 128 + c * 4;            // pixel column within the strip
+      uint32_t px[4];
+      bool okp[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int lx = lx0 + k, tile = lx >> 3, col = lx & 7;
+        const uint64_t x = sx0 + (uint64_t)lx;
+        okp[k] = tile < ntiles && x >= rc.x && x < rc.x + rc.w;
+        px[k] = 0;
+        if (!okp[k]) continue;
+        int Y, Cr, Cb;
+        strip_ycc(ys, crs, cbs, tile, r, col, Y, Cr, Cb);
+        px[k] = rgba_of(Y, Cr, Cb);
+      }
+      if (!(okp[0] || okp[1] || okp[2] || okp[3])) continue;
+      // the run's first column and its pixels in the order of their addresses
+      // (two's complement: a run that begins left of the rectangle has its
+      // missing pixels there, and those are not stored)
+      const uint64_t xo = sx0 + (uint64_t)lx0 - rc.x;
+      const uint64_t j0 = mirror ? rc.w - 4 - xo : xo;
+      uint32_t pm[4];
+      bool okm[4];
+#pragma unroll
+      for (int m = 0; m < 4; ++m) {
+        pm[m] = mirror ? px[3 - m] : px[m];
+        okm[m] = mirror ? okp[3 - m] : okp[m];
+      }
+      if constexpr (LAY == JPEGR_LAYOUT_CHW) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+          E e[4];
+#pragma unroll
+          for (int m = 0; m < 4; ++m)
+            e[m] = tensor_elem<DT>((pm[m] >> (8 * ch)) & 255u, nm.s[ch], nm.b[ch]);
+          store_run<E, 1>(base + (row0 + (uint64_t)ch * plane + j0), e, okm);
+        }
+      } else {
+        E e[12];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch)
+            e[3 * m + ch] = tensor_elem<DT>((pm[m] >> (8 * ch)) & 255u, nm.s[ch], nm.b[ch]);
+        }
+        store_run<E, 3>(base + (row0 + 3u * j0), e, okm);
+      }
     }
   }
 }

@@ -30,6 +30,10 @@
 //                 shape over the rectangles' cells, records found through the
 //                 caller's offsets), then jpeg_crop_recon_kernel (jpegr.hip);
 //                 the mapping is in jpegr_crop.h, the numbers in DESIGN 4.13
+//   jpegr_crop_tensor_device is the same call with elements for bytes:
+//                 jprs_crop_tensor_init (the capacity rule in elements),
+//                 jprs_crop_decode as it is, then jpeg_crop_tensor_kernel
+//                 (jpegr.hip); DESIGN 4.16
 //
 // The per-stream walk is the slot decoder's (jpegr_decode_common.h:
 // decode_stream / decode_stream_slow, the decode state, the carry-chain
@@ -38,6 +42,7 @@
 // every read is bounded by the stream's own length instead of whole 16-B
 // chunks.
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include "../../include/jpegr.h"
@@ -310,6 +315,34 @@ __global__ __launch_bounds__(256) void jprs_crop_init(
   status[r] = st;
 }
 
+// jprs_crop_init for jpegr_crop_tensor_device: dst and out_cap count elements,
+// a rectangle takes 3 w h of them, and no dst is misaligned.  (Its own text:
+// jprs_crop_init stays the code it was.)
+__global__ __launch_bounds__(256) void jprs_crop_tensor_init(
+    const uint8_t *__restrict__ in, uint64_t in_len, size_t ntiles, uint32_t w, uint32_t h,
+    uint32_t nimg, const jpegr_rect *__restrict__ rects, size_t nrects, size_t r_base,
+    uint32_t max_w, uint32_t max_h, uint64_t out_cap, uint32_t *__restrict__ status,
+    uint64_t *__restrict__ result) {
+  const size_t r = r_base + (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (r == 0) {
+    result[0] = 0ull;
+    result[1] = ~0ull;
+    result[2] = 0ull;
+  }
+  if (r >= nrects) return;
+  const jpegr_rect rc = rects[r];
+  uint32_t st = jpegr_crop::kGood;
+  if (!header_ok(in, in_len, ntiles, w, h, nimg, true))
+    st = jpegr_crop::kBad;
+  else if (rc.w == 0 || rc.h == 0)
+    st = jpegr_crop::kEmpty;
+  else if (rc.image >= nimg || rc.w > max_w || rc.h > max_h || rc.x > w || rc.w > w - rc.x ||
+           rc.y > h || rc.h > h - rc.y || rc.dst > out_cap ||
+           3 * rc.w * rc.h > out_cap - rc.dst)         // w, h < 2^31: the product cannot wrap
+    st = jpegr_crop::kBad;
+  status[r] = st;
+}
+
 // jprs_decode's shape -- 64 items a workgroup, a luma wave and a chroma wave --
 // over the rectangles' cells: item i is cell i % K of rectangle i / K.  A lane
 // finds its record through toff, the caller's offsets, which are not trusted:
@@ -434,4 +467,43 @@ extern "C" int jpegr_crop_device(const void *d_in, size_t in_len, int w, int h, 
   });
   return jpegr_crop_recon_launch(coef, status, rects, nrects, max_w, max_h,
                                  static_cast<uint8_t *>(d_out), result, st);
+}
+
+extern "C" int jpegr_crop_tensor_device(const void *d_in, size_t in_len, int w, int h, int nimg,
+                                        const void *d_tile_offsets, const void *d_rects,
+                                        size_t nrects, const void *d_flip, int max_w, int max_h,
+                                        int dtype, int layout, const float *scale3,
+                                        const float *bias3, void *d_out, size_t out_cap,
+                                        void *d_scratch, void *d_result, void *stream) {
+  const size_t ntiles = tiles_of(w, h, nimg);
+  const size_t K = jpegr_crop_items(max_w, max_h);
+  if (!d_in || !d_tile_offsets || !d_rects || !d_out || !d_scratch || !d_result || ntiles == 0 ||
+      nrects == 0 || K == 0 || max_w > w || max_h > h || in_len < (size_t)kHdr || misaligned(d_rects, 7) ||
+      misaligned(d_tile_offsets, 7) || misaligned(d_result, 7) || misaligned(d_scratch, 15) ||
+      misaligned(d_out, 15) || dtype < JPEGR_DTYPE_U8 || dtype > JPEGR_DTYPE_BF16 ||
+      (layout != JPEGR_LAYOUT_CHW && layout != JPEGR_LAYOUT_HWC) ||
+      nrects > kMaxWg * kLanes / K)                   // one launch_chunks pass: 2^28 items
+    return JPEGR_ERR_ARG;
+  for (int c = 0; c < 3; ++c)
+    if ((scale3 && !isfinite(scale3[c])) || (bias3 && !isfinite(bias3[c]))) return JPEGR_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  auto *in = static_cast<const uint8_t *>(d_in);
+  auto *rects = static_cast<const jpegr_rect *>(d_rects);
+  auto *result = static_cast<uint64_t *>(d_result);
+  auto *coef = static_cast<int16_t *>(d_scratch);
+  auto *status = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_scratch) + nrects * K * 256);
+  launch_chunks(nrects, 256, [&](size_t b, unsigned n) {
+    hipLaunchKernelGGL(jprs_crop_tensor_init, dim3(n), dim3(256), 0, st, in, (uint64_t)in_len, ntiles,
+                       (uint32_t)w, (uint32_t)h, (uint32_t)nimg, rects, nrects, b * 256,
+                       (uint32_t)max_w, (uint32_t)max_h, (uint64_t)out_cap, status, result);
+  });
+  launch_chunks(nrects * K, kLanes, [&](size_t b, unsigned n) {
+    hipLaunchKernelGGL(jprs_crop_decode, dim3(n), dim3(2 * kLanes), 0, st, in, (uint64_t)in_len,
+                       (uint32_t)((w + 7) / 8), (uint32_t)((h + 7) / 8),
+                       static_cast<const uint64_t *>(d_tile_offsets), rects, nrects, (uint32_t)K, b,
+                       status, result, coef);
+  });
+  return jpegr_crop_tensor_launch(coef, status, rects, nrects, max_w, max_h,
+                                  static_cast<const uint8_t *>(d_flip), dtype, layout, scale3, bias3,
+                                  d_out, result, st);
 }

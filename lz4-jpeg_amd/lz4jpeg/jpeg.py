@@ -374,6 +374,105 @@ def crop_device(d_stream, in_len, w, h, nimg, d_offsets, d_image, d_x, d_y, d_w,
     return d_out, d_dst, n
 
 
+# jpegr.h's JPEGR_LAYOUT_* by name
+_LAYOUTS = {"chw": 0, "hwc": 1}
+
+
+def _tensor_dtype(dtype):
+    """(the torch dtype, jpegr.h's JPEGR_DTYPE_* of it); None is float32."""
+    import torch
+    codes = {torch.uint8: 0, torch.float32: 1, torch.float16: 2, torch.bfloat16: 3}
+    dtype = torch.float32 if dtype is None else dtype
+    if dtype not in codes:
+        raise ValueError("dtype is none of torch.uint8, float32, float16 and bfloat16")
+    return dtype, codes[dtype]
+
+
+def _three(v, name):
+    """One value or three as a list of three Python floats."""
+    try:
+        vals = [float(x) for x in v]
+    except TypeError:
+        vals = [float(v)]
+    if len(vals) == 1:
+        vals = vals * 3
+    if len(vals) != 3:
+        raise ValueError(f"{name} is one float or three")
+    return vals
+
+
+def _float3(v, name):
+    """None (NULL), or the call's three floats: each rounded once to float32."""
+    return None if v is None else (ctypes.c_float * 3)(*_three(v, name))
+
+
+def normalisation(mean=None, std=None):
+    """(scale, bias), three float32 values each as Python floats, such that
+    fl32(fl32(v * scale) + bias) normalises a byte v: scale = 1 / (255 std) and
+    bias = -mean / std, computed in Python floats and rounded once to float32;
+    None is a mean of 0 and a std of 1.  mean, std: one float or three."""
+    mean = [0.0] * 3 if mean is None else _three(mean, "mean")
+    std = [1.0] * 3 if std is None else _three(std, "std")
+    return ([float(np.float32(1.0 / (255.0 * s))) for s in std],
+            [float(np.float32(0.0 - m / s)) for m, s in zip(mean, std)])
+
+
+def crop_tensor_device(d_stream, in_len, w, h, nimg, d_offsets, d_image, d_x, d_y, d_w, d_h, max_w, max_h,
+                       d_dst=None, d_out=None, out_cap=None, scratch=None, d_result=None, stream=None,
+                       check=True, dtype=None, layout="chw", scale=None, bias=None, d_flip=None):
+    """crop_device's rectangles as what a model reads, in one call
+    (jpegr_crop_tensor_device): three channels (alpha dropped) of `dtype`
+    (torch.float32, the default, float16, bfloat16 or uint8), planar
+    (layout="chw": [3, h, w] a crop) or interleaved ("hwc": [h, w, 3]).  Channel
+    c of a pixel's byte v becomes fl32(fl32(v * scale[c]) + bias[c]), two
+    rounded float32 operations -- what x.float().mul(scale).add(bias) gives --
+    then rounded to nearest-even to `dtype`; uint8 delivers v and ignores both.
+    scale, bias: one float or three, None for 1 and 0.  d_flip: None, or a bool
+    or uint8 tensor with an entry per crop, nonzero to mirror that crop
+    horizontally.  The other arguments are crop_device's, with d_dst and
+    out_cap counting elements of `dtype` in d_out (a tensor of that dtype): a
+    crop takes 3 w h of them, and d_dst=None packs the crops back to back.
+    Returns (d_out, d_dst, delivered); raises JpegError naming the first bad
+    rectangle; check=False does no read-back and returns None for the count."""
+    import torch
+    dtype, code = _tensor_dtype(dtype)
+    if layout not in _LAYOUTS:
+        raise ValueError('layout is "chw" or "hwc"')
+    scale3, bias3 = _float3(scale, "scale"), _float3(bias, "bias")
+    nrects = d_x.numel()
+    if d_flip is not None and (d_flip.dtype not in (torch.bool, torch.uint8) or d_flip.numel() != nrects):
+        raise ValueError("d_flip is a bool or uint8 tensor with one entry per crop")
+    if d_out is not None and d_out.dtype != dtype:
+        raise ValueError("d_out is not of the requested dtype")
+    if d_dst is None:
+        d_len = 3 * d_w * d_h
+        d_dst = torch.cumsum(d_len, 0) - d_len
+    if out_cap is None:
+        if d_out is not None:
+            out_cap = d_out.numel()
+        elif check and nrects:
+            out_cap = int((d_dst + 3 * d_w * d_h).max().item())
+        else:
+            out_cap = nrects * 3 * max_w * max_h
+    dev = d_stream.device
+    d_out = _buffer(d_out, out_cap, dtype, dev, "d_out smaller than out_cap elements", floor=4)
+    if nrects == 0:
+        return d_out, d_dst, (0 if check else None)
+    _check_in_len(d_stream, in_len)
+    _check_offsets(d_offsets, nimg * tiles(w, h))
+    d_rects = torch.stack((d_image, d_x, d_y, d_w, d_h, d_dst), dim=1).contiguous()
+    scratch = _buffer(scratch, crop_scratch_bytes(nrects, max_w, max_h), torch.uint8, dev,
+                      "scratch smaller than crop_scratch_bytes(nrects, max_w, max_h)", floor=16)
+    d_result = _buffer(d_result, 3, torch.int64, dev)
+    _call("jpegr_crop_tensor_device", d_stream, in_len, w, h, nimg, d_offsets, d_rects, nrects, d_flip,
+          max_w, max_h, code, _LAYOUTS[layout], scale3, bias3, d_out, out_cap, scratch, d_result,
+          stream_arg(stream))
+    if not check:
+        return d_out, d_dst, None
+    n = _lib.batch_verdict(d_result, stream, JpegError, -1, "jpegr_crop_tensor_device: rectangle")
+    return d_out, d_dst, n
+
+
 # -- thumbnails -----------------------------------------------------------------
 def thumb_device(d_stream, in_len, w, h, nimg, first=0, count=None, d_offsets=None, d_out=None,
                  d_dc=None, want_dc=False, scratch=None, d_result=None, stream=None):
@@ -546,6 +645,38 @@ class StreamReader:
         """crop_device on this stream: (d_out, d_dst, delivered)."""
         return crop_device(self.d_stream, self.length, self.w, self.h, self.nimg, self.d_offsets,
                            d_image, d_x, d_y, d_w, d_h, max_w, max_h, **kw)
+
+    def crops_tensor(self, d_image, d_x, d_y, d_w, d_h, max_w, max_h, **kw):
+        """crop_tensor_device on this stream: (d_out, d_dst, delivered)."""
+        return crop_tensor_device(self.d_stream, self.length, self.w, self.h, self.nimg, self.d_offsets,
+                                  d_image, d_x, d_y, d_w, d_h, max_w, max_h, **kw)
+
+    def crop_batch(self, d_image, d_x, d_y, w, h, dtype=None, layout="chw", mean=None, std=None,
+                   d_flip=None):
+        """n crops of w x h pixels, crop r from (d_x[r], d_y[r]) of image
+        d_image[r], as one normalised tensor of `dtype` (default float32):
+        [n, 3, h, w] with layout="chw", [n, h, w, 3] with "hwc"; d_flip as for
+        crop_tensor_device.  Channel c of a pixel's byte v becomes
+        fl32(fl32(v * scale[c]) + bias[c]) with scale = 1 / (255 std) and
+        bias = -mean / std (normalisation(): computed in Python floats, rounded
+        once to float32), two rounded float32 operations, then rounded to
+        `dtype`.  mean and std of None: scale 1 / 255 and bias 0.  This is not
+        bit-identical to ToTensor followed by Normalize, which divide (by 255,
+        then by std) where this multiplies."""
+        import torch
+        dtype, _ = _tensor_dtype(dtype)
+        if layout not in _LAYOUTS:
+            raise ValueError('layout is "chw" or "hwc"')
+        scale, bias = normalisation(mean, std)
+        n, dev = d_x.numel(), self.d_stream.device
+        shape = (n, 3, h, w) if layout == "chw" else (n, h, w, 3)
+        d_out = torch.empty(n * 3 * w * h, dtype=dtype, device=dev)
+        if n and w and h:
+            d_dst = torch.arange(n, dtype=torch.int64, device=dev) * (3 * w * h)
+            self.crops_tensor(d_image, d_x, d_y, torch.full_like(d_x, w), torch.full_like(d_x, h), w, h,
+                              d_dst=d_dst, d_out=d_out, out_cap=d_out.numel(), dtype=dtype,
+                              layout=layout, scale=scale, bias=bias, d_flip=d_flip)
+        return d_out.view(shape)
 
     def thumbnails(self, first=0, count=None):
         """thumbnails_device on this stream, through the kept offsets: (uint8

@@ -7,7 +7,7 @@ launches.
     python tools/jpeg_pack_bench.py [--steps K] [--once N]
                                     [--decode | --tight [--against LIB] | --direct [--against LIB]
                                      | --crop [--against LIB] | --thumb [--against LIB]
-                                     | --select [--against LIB]]
+                                     | --select [--against LIB] | --tensor [--against LIB]]
 
 Images: bench.py's 3840x2160 random image (synth.rand_rgba_device, seed 1)
 and a 3840x2160 smooth one (tests/test_gpu_entropy.py's generator).  Prints
@@ -95,7 +95,19 @@ calls.  All in this run after the same pre-warm and settle, alternated over
 --rounds rounds, event-timed.  --against LIB times the five select calls of this
 build and of a second build of the library in the same rounds, both by the same
 bare C call, outputs compared, and prints each pair's ratio of the medians.  With --once N: N select calls of each kind
-per stream and nothing else."""
+per stream and nothing else.
+
+--tensor: crops delivered as normalised tensors (jpegr_crop_tensor_device), for
+profiles/jpr_tensor_bench.md: --crop's streams and rectangles, the index built
+once outside the timed calls.  The fused call as float32 CHW and as bfloat16
+CHW, ImageNet's normalisation, every second crop mirrored; beside each, in the
+same rounds, crop_device followed by the torch chain it replaces (slice off the
+alpha, permute, float, mul, add, to(bfloat16), where / flip); and crop_device
+alone.  The fused outputs are compared bitwise with the chain's before anything
+is timed.  --against LIB times crop_device of this build and of a second build
+in the same rounds, both by the same bare C call, outputs compared.  All after
+the same pre-warm and settle, alternated over --rounds rounds, event-timed.
+With --once N: N fused calls of each dtype per stream and nothing else."""
 import argparse
 import json
 import os
@@ -714,6 +726,122 @@ def crop_side(args, torch, jpeg, synth, dev, other):
             del d_stream
 
 
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+def tensor_side(args, torch, jpeg, synth, dev, other):
+    """Crops delivered as normalised tensors (jpegr_crop_tensor_device) beside
+    crop_device followed by the torch chain it replaces, and crop_device alone."""
+    nt = CN * jpeg.tiles(CW, CH)
+    px = CW * CH
+    rng = np.random.default_rng(7)                          # --crop's rectangles
+    im = rng.integers(0, CN, NCROPS)
+    x = rng.integers(0, CW - CROP + 1, NCROPS)
+    y = rng.integers(0, CH - CROP + 1, NCROPS)
+    t64 = lambda a: torch.from_numpy(np.asarray(a, np.int64)).to(dev)
+    cols = [t64(im), t64(x), t64(y), t64(np.full(NCROPS, CROP)), t64(np.full(NCROPS, CROP))]
+    d_dst4 = t64(np.arange(NCROPS) * 4 * CROP * CROP)
+    d_dst3 = t64(np.arange(NCROPS) * 3 * CROP * CROP)
+    cap4, cap3 = NCROPS * 4 * CROP * CROP, NCROPS * 3 * CROP * CROP
+    d_flip = torch.from_numpy((np.arange(NCROPS) % 2).astype(np.uint8)).to(dev)      # half mirrored
+    mask = d_flip.bool().view(NCROPS, 1, 1, 1)
+    scale, bias = jpeg.normalisation(IMAGENET_MEAN, IMAGENET_STD)
+    d_scale, d_bias = (torch.tensor(v, dtype=torch.float32, device=dev).view(1, 3, 1, 1) for v in (scale, bias))
+    images = {}
+    d_img = torch.empty(CN * px * 4, dtype=torch.uint8, device=dev)
+    synth.rand_rgba_device(d_img, 0, CN * px, seed=1)
+    images["random"] = d_img
+    images["smooth"] = torch.from_numpy(smooth_image(CW, CH)).to(dev).reshape(-1).repeat(CN)
+    d_offs = torch.empty(nt + 1, dtype=torch.int64, device=dev)
+    d_ires = torch.empty(2, dtype=torch.int64, device=dev)
+    d_res, d_tres = (torch.empty(3, dtype=torch.int64, device=dev) for _ in range(2))
+    iscr = torch.empty(int(jpeg._lib.lib().jpegr_pack_scratch_bytes(nt)), dtype=torch.uint8, device=dev)
+    cscr = torch.empty(jpeg.crop_scratch_bytes(NCROPS, CROP, CROP), dtype=torch.uint8, device=dev)
+    d_rgba = torch.empty(cap4, dtype=torch.uint8, device=dev)
+    d_f32 = torch.empty(cap3, dtype=torch.float32, device=dev)
+    d_bf16 = torch.empty(cap3, dtype=torch.bfloat16, device=dev)
+    for name, img in images.items():
+        for tight in (False, True):
+            d_stream = jpeg.compress_device(img, CW, CH, CN, tight=tight)
+            n = d_stream.numel()
+            jpeg.stream_index_device(d_stream, n, CW, CH, CN, d_offsets=d_offs, d_result=d_ires, scratch=iscr)
+
+            def crops():
+                jpeg.crop_device(d_stream, n, CW, CH, CN, d_offs, *cols, CROP, CROP, d_dst=d_dst4,
+                                 d_out=d_rgba, out_cap=cap4, scratch=cscr, d_result=d_res, check=False)
+
+            def tensor(d_out, dtype):
+                jpeg.crop_tensor_device(d_stream, n, CW, CH, CN, d_offs, *cols, CROP, CROP, d_dst=d_dst3,
+                                        d_out=d_out, out_cap=cap3, scratch=cscr, d_result=d_tres,
+                                        check=False, dtype=dtype, layout="chw", scale=scale, bias=bias,
+                                        d_flip=d_flip)
+
+            def chain(dtype):
+                crops()
+                t = d_rgba.view(NCROPS, CROP, CROP, 4)[..., :3].permute(0, 3, 1, 2).float()
+                t = t.mul(d_scale).add(d_bias)
+                if dtype != torch.float32:
+                    t = t.to(dtype)
+                return torch.where(mask, t.flip(3), t)
+
+            calls = [("tensor_f32", lambda: tensor(d_f32, torch.float32)),
+                     ("tensor_bf16", lambda: tensor(d_bf16, torch.bfloat16)),
+                     ("chain_f32", lambda: chain(torch.float32)),
+                     ("chain_bf16", lambda: chain(torch.bfloat16)),
+                     ("crops", crops)]
+            if args.once:
+                for _ in range(args.once):
+                    calls[0][1]()
+                    calls[1][1]()
+                torch.cuda.synchronize()
+                continue
+            calls[0][1]()
+            ok = d_tres.cpu().tolist() == [NCROPS, -1, 0]
+            calls[1][1]()
+            ok = ok and d_tres.cpu().tolist() == [NCROPS, -1, 0]
+            ok = ok and bool(torch.equal(d_f32.view(NCROPS, 3, CROP, CROP).view(torch.int32),
+                                         chain(torch.float32).contiguous().view(torch.int32)))
+            ok = ok and bool(torch.equal(d_bf16.view(NCROPS, 3, CROP, CROP).view(torch.int16),
+                                         chain(torch.bfloat16).contiguous().view(torch.int16)))
+            ok = ok and d_ires.cpu().tolist() == [n, -1] and d_res.cpu().tolist() == [NCROPS, -1, 0]
+            res = {"stream": f"{name} {CN} x {CW}x{CH} {'JPT1' if tight else 'JPR1'}",
+                   "crops": f"{NCROPS} of {CROP}x{CROP}, every second one mirrored", "outputs_equal": ok,
+                   "steps": args.steps, "rounds": args.rounds, "rgba_bytes": cap4, "f32_bytes": 4 * cap3,
+                   "bf16_bytes": 2 * cap3}
+            if other is not None:         # crop_device of either build by the same bare C call
+                import ctypes
+                vp = lambda t: ctypes.c_void_p(t.data_ptr())
+                st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+                a_rgba, a_res = torch.empty_like(d_rgba), torch.empty_like(d_res)
+                rects = torch.stack((*cols, d_dst4), dim=1).contiguous()
+
+                def crops_on(lib, out, r):
+                    checked(lib.jpegr_crop_device(vp(d_stream), n, CW, CH, CN, vp(d_offs), vp(rects), NCROPS,
+                                                  CROP, CROP, vp(out), cap4, vp(cscr), vp(r), st))
+
+                calls += [("bare_crops", lambda: crops_on(jpeg._lib.lib(), d_rgba, d_res)),
+                          ("against_bare_crops", lambda: crops_on(other, a_rgba, a_res))]
+                calls[-2][1]()
+                calls[-1][1]()
+                torch.cuda.synchronize()
+                res["against_outputs_equal"] = bool(torch.equal(a_rgba, d_rgba)) and bool(torch.equal(a_res, d_res))
+            ms = {k: [] for k, _ in calls}
+            for r in range(args.rounds):                  # alternated; the order turns with the round
+                for key, fn in calls[r % len(calls):] + calls[:r % len(calls)]:
+                    settle(fn, torch.cuda.synchronize, chunk=4)
+                    ms[key].append(timed(fn, args.steps, torch))
+            for key, _ in calls:
+                res[key + "_ms"] = spread(ms[key])
+            med = lambda k: res[k + "_ms"]["median"]
+            if other is not None:
+                over_against(res, ["bare_crops"])
+            for d in ("f32", "bf16"):
+                res[f"tensor_{d}_over_chain_{d}"] = round(med("tensor_" + d) / med("chain_" + d), 4)
+                res[f"tensor_{d}_over_crops"] = round(med("tensor_" + d) / med("crops"), 4)
+            print(json.dumps(res), flush=True)
+            del d_stream
+
+
 def thumb_side(args, torch, jpeg, synth, dev, other):
     """Thumbnails straight from the stream beside decode-everything-and-pool."""
     import ctypes
@@ -995,8 +1123,9 @@ def main():
     ap.add_argument("--crop", action="store_true")
     ap.add_argument("--thumb", action="store_true")
     ap.add_argument("--select", action="store_true")
+    ap.add_argument("--tensor", action="store_true")
     ap.add_argument("--against", default=None,
-                    help="with --tight, --direct, --crop or --select: a second liblz4jpeg.so to "
+                    help="with --tight, --direct, --crop, --select or --tensor: a second liblz4jpeg.so to "
                          "alternate with; with --thumb: that, or a second build of jpegr_thumb.hip "
                          "alone (make thumb-alt)")
     args = ap.parse_args()
@@ -1005,12 +1134,14 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("jpeg_pack_bench: needs a GPU (there is no CPU path to time)")
     dev = torch.device("cuda:0")
-    if args.crop or args.thumb or args.select:
+    if args.crop or args.thumb or args.select or args.tensor:
         if not args.once:                   # clock pre-warm (bench.py run_lz4)
             d_warm = torch.zeros(256 << 20, dtype=torch.uint8, device=dev)
             settle(lambda: d_warm.add_(1), torch.cuda.synchronize, ms=100.0, chunk=16)
             del d_warm
-        if args.crop:
+        if args.tensor:
+            tensor_side(args, torch, jpeg, synth, dev, second_build(args.against) if args.against else None)
+        elif args.crop:
             crop_side(args, torch, jpeg, synth, dev, second_build(args.against) if args.against else None)
         elif args.select:
             select_side(args, torch, jpeg, synth, dev, second_build(args.against) if args.against else None)

@@ -476,6 +476,78 @@ int jpegr_crop_tensor_device(const void *d_in, size_t in_len, int w, int h, int 
                              void *d_out, size_t out_cap,
                              void *d_scratch, void *d_result, void *stream);
 
+/* jpegr_crop_resize_device: rectangles of different sizes, each resampled to
+ * out_w x out_h and delivered as jpegr_crop_tensor_device delivers (what
+ * RandomResizedCrop, ToTensor, Normalize and a flip do), in five launches.
+ * From jpegr_crop_tensor_device, unchanged: d_rects (jpegr_rect), the
+ * untrusted d_tile_offsets, the K = jpegr_crop_items(max_w, max_h) mapping and
+ * its 2^28 limit, d_flip, dtype, layout, the host scale3 / bias3 passed by
+ * value, the three result words; asynchronous on `stream`, no read-back, no
+ * host state, capturable and replayable, several calls in flight; every "no
+ * read leaves / no write leaves" guarantee (the scratch here being
+ * jpegr_crop_resize_scratch_bytes(nrects, max_w, max_h, out_w, out_h) bytes,
+ * 16-B aligned), and JPEGR_ERR_ARG before any HIP call.
+ * Differences.  Rectangle r's source is pixels [x, x + w) x [y, y + h) of its
+ * image; each has its own w <= max_w and h <= max_h.  Its output is
+ * 3 out_w out_h elements at d_out + dst (dst and out_cap count elements; d_out
+ * 16-B aligned): CHW three planes of out_h rows of out_w; HWC pixel (i, j) at
+ * dst + 3 (i out_w + j).  Rectangles at dst = r * 3 out_w out_h form
+ * [n, 3, out_h, out_w] or [n, out_h, out_w, 3].  A rectangle is bad by
+ * jpegr_crop_tensor_device's rules with the capacity rule
+ * dst + 3 out_w out_h > out_cap, and also when w == 0 or h == 0 (nothing to
+ * resample: no rectangle is "empty" in this call).  One that is bad on its own
+ * fields or on the header writes nothing; one that fails inside a tile may
+ * leave unspecified values in its own elements; good rectangles are exact
+ * whatever the bad ones do.  JPEGR_ERR_ARG also for out_w or out_h <= 0,
+ * 3 * out_w * out_h past INT_MAX, and a filter that is neither value below.
+ * jpegr_crop_resize_scratch_bytes returns 0 on a bad argument (or a size past
+ * SIZE_MAX) and is monotone in nrects.
+ *
+ * Values: the whole contract, bit for bit reproducible in numpy.  Per axis,
+ * with n source pixels and m output pixels, in fp64, every operation rounded
+ * and never fused:
+ *   r  = (double)n / (double)m
+ *   s  = (filter == TRIANGLE && r > 1.0) ? r : 1.0
+ *   for output index j:
+ *     c   = ((double)j + 0.5) * r
+ *     lo  = max(0, (int64)floor((c - s) + 0.5));  hi = min(n, (int64)floor((c + s) + 0.5))
+ *     u_x = max(0.0, 1.0 - fabs(((double)x + 0.5) - c) / s)     for x = lo .. hi - 1
+ *     tot = ((0.0 + u_lo) + u_lo+1) + ...                       ascending x
+ *     wt_x = (float)(u_x / tot)                 fp64 divide, then one rounding to fp32
+ * hi > lo and tot >= 0.5 always: the pixel nearest to c is within 0.5 of it.
+ * Then the pixels, per channel c (0 R, 1 G, 2 B) of the bytes v that
+ * jpegr_crop_device delivers for the rectangle, in fp32, horizontal first:
+ *   mid[y][j] = acc after: acc = 0.0f; for x = lo_j .. hi_j - 1 ascending:
+ *                          acc = fl32(acc + fl32(wtx_x * (float)v[y][x]))
+ *   val[i][j] = acc after: acc = 0.0f; for y = lo_i .. hi_i - 1 ascending:
+ *                          acc = fl32(acc + fl32(wty_y * mid[y][j]))
+ * A zero-weight tap changes nothing (acc + 0 = acc), so skipping it is within
+ * the contract.  fp32 subnormals are kept, in weights and products alike.
+ * The element: JPEGR_DTYPE_U8: val rounded to nearest-even and clamped to
+ * 0 .. 255, scale3 and bias3 ignored.  Otherwise
+ *   f = fl32(fl32(val * scale3[c]) + bias3[c]),
+ * stored as F32, or rounded to nearest-even to F16 / BF16 exactly as
+ * jpegr_crop_tensor_device does; val is not rounded to a byte first.
+ * A nonzero d_flip[r] mirrors the OUTPUT: output column j holds resampled
+ * column out_w - 1 - j.
+ * Two consequences.  With w == out_w and h == out_h every wt is exactly 1.0 or
+ * 0.0, and with either filter the elements equal jpegr_crop_tensor_device's bit
+ * for bit.  And the definition is the half-pixel-centre bilinear of
+ * interpolate(mode="bilinear", align_corners=False, antialias=<filter>), from
+ * which it differs by roundings only (tests/test_jpr_resize_model.py). */
+#define JPEGR_FILTER_BILINEAR 0   /* triangle filter, support 1: 2 taps an axis */
+#define JPEGR_FILTER_TRIANGLE 1   /* antialiased: support max(1, n / m) */
+
+size_t jpegr_crop_resize_scratch_bytes(size_t nrects, int max_w, int max_h,
+                                       int out_w, int out_h);
+int jpegr_crop_resize_device(const void *d_in, size_t in_len, int w, int h, int nimg,
+                             const void *d_tile_offsets, const void *d_rects, size_t nrects,
+                             const void *d_flip, int max_w, int max_h,
+                             int out_w, int out_h, int filter,
+                             int dtype, int layout, const float *scale3, const float *bias3,
+                             void *d_out, size_t out_cap,
+                             void *d_scratch, void *d_result, void *stream);
+
 /* Thumbnails: images [image0, image0 + nimage) of a JPR1 or JPT1 stream at 1/8
  * scale, one RGBA8 pixel per tile, from the tiles' DC terms alone.  With
  * gw = ceil(w / 8) and gh = ceil(h / 8), pixel (tx, ty) of an image's

@@ -6,6 +6,8 @@
 // of jpegr_crop_tensor_device, which delivers elements of a tensor).
 #pragma once
 
+#include "jpegr_tensor_elem.h"
+
 #pragma clang fp contract(off)
 
 namespace {
@@ -273,41 +275,8 @@ __global__ __launch_bounds__(kThreads) void jpeg_crop_recon_kernel(
 }
 
 // ---- crops as tensors (jpegr_crop_tensor_device, include/jpegr.h) -------------
-// The element of one channel byte v: U8 the byte; otherwise
-// f = fl32(fl32((float)v * s) + b), two fp32 operations each rounded (no
-// contraction in this file), stored as fp32 bits, or rounded to nearest-even
-// to f16 (the hardware conversion, subnormals kept) or to bf16 (on the fp32
-// bits; f is never a NaN: v and s, b are finite).
-template <int DT>
-struct TensorElem {
-  using type = uint16_t;
-};
-template <>
-struct TensorElem<JPEGR_DTYPE_U8> {
-  using type = uint8_t;
-};
-template <>
-struct TensorElem<JPEGR_DTYPE_F32> {
-  using type = uint32_t;
-};
-
-template <int DT>
-__device__ __forceinline__ typename TensorElem<DT>::type tensor_elem(uint32_t v, float s, float b) {
-  if constexpr (DT == JPEGR_DTYPE_U8) {
-    return (uint8_t)v;
-  } else {
-    const float p = (float)v * s;
-    const float f = p + b;
-    if constexpr (DT == JPEGR_DTYPE_F32) {
-      return __float_as_uint(f);
-    } else if constexpr (DT == JPEGR_DTYPE_F16) {
-      return __builtin_bit_cast(uint16_t, (_Float16)f);
-    } else {
-      const uint32_t u = __float_as_uint(f);
-      return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-    }
-  }
-}
+// The element, its type and the normalisation (TensorElem, tensor_elem,
+// TensorNorm): jpegr_tensor_elem.h.
 
 // B bytes (dwords wd) to p, whose address is A0 mod 16 (A0 a multiple of 4):
 // from the front, the widest of 16, 8 and 4 B that the address there and the
@@ -366,12 +335,6 @@ __device__ __forceinline__ void store_run(E *q, const E (&e)[4 * C], const bool 
       }
   }
 }
-
-// scale3 and bias3 of the call, by value: kernel arguments, so a captured
-// launch keeps them
-struct TensorNorm {
-  float s[3], b[3];
-};
 
 // jpeg_crop_recon_kernel's workgroup, phases 1 and 2 and verdict counting, with
 // another phase 3: the pixel's R, G and B become elements of DT (tensor_elem),

@@ -34,6 +34,11 @@
 //                 jprs_crop_tensor_init (the capacity rule in elements),
 //                 jprs_crop_decode as it is, then jpeg_crop_tensor_kernel
 //                 (jpegr.hip); DESIGN 4.16
+//   jpegr_crop_resize_device resamples the rectangles to one size: its own
+//                 first launch and last two are jpegr_resize.hip's
+//                 (jpegr_resize.h); between them jprs_crop_decode and
+//                 jpeg_crop_recon_kernel as they are, on shadow rectangles
+//                 whose pixels go to the scratch; DESIGN 4.17
 //
 // The per-stream walk is the slot decoder's (jpegr_decode_common.h:
 // decode_stream / decode_stream_slow, the decode state, the carry-chain
@@ -49,6 +54,7 @@
 #include "jpegr_crop.h"
 #include "jpegr_decode_common.h"
 #include "jpegr_pack_common.h"
+#include "jpegr_resize.h"
 
 namespace {
 
@@ -506,4 +512,48 @@ extern "C" int jpegr_crop_tensor_device(const void *d_in, size_t in_len, int w, 
   return jpegr_crop_tensor_launch(coef, status, rects, nrects, max_w, max_h,
                                   static_cast<const uint8_t *>(d_flip), dtype, layout, scale3, bias3,
                                   d_out, result, st);
+}
+
+extern "C" int jpegr_crop_resize_device(const void *d_in, size_t in_len, int w, int h, int nimg,
+                                        const void *d_tile_offsets, const void *d_rects,
+                                        size_t nrects, const void *d_flip, int max_w, int max_h,
+                                        int out_w, int out_h, int filter, int dtype, int layout,
+                                        const float *scale3, const float *bias3, void *d_out,
+                                        size_t out_cap, void *d_scratch, void *d_result, void *stream) {
+  const size_t ntiles = tiles_of(w, h, nimg);
+  const size_t K = jpegr_crop_items(max_w, max_h);
+  if (!d_in || !d_tile_offsets || !d_rects || !d_out || !d_scratch || !d_result || ntiles == 0 ||
+      nrects == 0 || K == 0 || max_w > w || max_h > h || in_len < (size_t)kHdr || misaligned(d_rects, 7) ||
+      misaligned(d_tile_offsets, 7) || misaligned(d_result, 7) || misaligned(d_scratch, 15) ||
+      misaligned(d_out, 15) || dtype < JPEGR_DTYPE_U8 || dtype > JPEGR_DTYPE_BF16 ||
+      (layout != JPEGR_LAYOUT_CHW && layout != JPEGR_LAYOUT_HWC) ||
+      (filter != JPEGR_FILTER_BILINEAR && filter != JPEGR_FILTER_TRIANGLE) || out_w <= 0 || out_h <= 0 ||
+      (long long)out_w * out_h > 0x7fffffffll / 3 ||  // a rectangle's 3 out_w out_h elements fit an int
+      nrects > kMaxWg * kLanes / K)                   // one launch_chunks pass: 2^28 items
+    return JPEGR_ERR_ARG;
+  for (int c = 0; c < 3; ++c)
+    if ((scale3 && !isfinite(scale3[c])) || (bias3 && !isfinite(bias3[c]))) return JPEGR_ERR_ARG;
+  jpegr_resize::Layout L;
+  if (!jpegr_resize::layout_of(nrects, max_w, max_h, out_w, out_h, L)) return JPEGR_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  auto *in = static_cast<const uint8_t *>(d_in);
+  auto *rects = static_cast<const jpegr_rect *>(d_rects);
+  auto *result = static_cast<uint64_t *>(d_result);
+  auto *base = static_cast<uint8_t *>(d_scratch);
+  auto *coef = static_cast<int16_t *>(d_scratch);
+  auto *status = reinterpret_cast<uint32_t *>(base + L.status);
+  auto *shadow = reinterpret_cast<const jpegr_rect *>(base + L.shadow);
+  jpegr_resize_init_launch(in, in_len, ntiles, w, h, nimg, rects, nrects, max_w, max_h, out_w, out_h,
+                           out_cap, L, d_scratch, result, st);
+  launch_chunks(nrects * K, kLanes, [&](size_t b, unsigned n) {
+    hipLaunchKernelGGL(jprs_crop_decode, dim3(n), dim3(2 * kLanes), 0, st, in, (uint64_t)in_len,
+                       (uint32_t)((w + 7) / 8), (uint32_t)((h + 7) / 8),
+                       static_cast<const uint64_t *>(d_tile_offsets), shadow, nrects, (uint32_t)K, b,
+                       status, result, coef);
+  });
+  if (jpegr_crop_recon_launch(coef, status, shadow, nrects, max_w, max_h, base + L.pix, result, st) !=
+      JPEGR_OK)
+    return JPEGR_ERR_HIP;
+  return jpegr_resize_launch(L, d_scratch, rects, nrects, out_w, out_h, filter,
+                             static_cast<const uint8_t *>(d_flip), dtype, layout, scale3, bias3, d_out, st);
 }

@@ -473,6 +473,63 @@ def crop_tensor_device(d_stream, in_len, w, h, nimg, d_offsets, d_image, d_x, d_
     return d_out, d_dst, n
 
 
+def crop_resize_scratch_bytes(nrects, max_w, max_h, out_w, out_h):
+    return int(_lib.call("jpegr_crop_resize_scratch_bytes", nrects, max_w, max_h, out_w, out_h))
+
+
+def crop_resize_device(d_stream, in_len, w, h, nimg, d_offsets, d_image, d_x, d_y, d_w, d_h, max_w, max_h,
+                       out_w, out_h, antialias=True, d_dst=None, d_out=None, out_cap=None, scratch=None,
+                       d_result=None, stream=None, check=True, dtype=None, layout="chw", scale=None,
+                       bias=None, d_flip=None):
+    """crop_tensor_device's rectangles, each of its own size, resampled to
+    out_w x out_h in the same call (jpegr_crop_resize_device): the half-pixel
+    bilinear of interpolate(mode="bilinear", align_corners=False), with
+    antialias=True (the default, JPEGR_FILTER_TRIANGLE) widening the filter by
+    the scale when a rectangle is larger than the output; include/jpegr.h
+    states the arithmetic, which numpy reproduces bit for bit.  The resampled
+    value is normalised without being rounded to a byte first; uint8 rounds it
+    to nearest-even.  d_flip mirrors the output.  A crop takes 3 out_w out_h
+    elements of `dtype`, d_dst=None packs them back to back, and a rectangle
+    with w or h of 0 is bad.  The scratch is crop_resize_scratch_bytes(nrects,
+    max_w, max_h, out_w, out_h) bytes.  Everything else, the returns and
+    check=False included, is crop_tensor_device's."""
+    import torch
+    dtype, code = _tensor_dtype(dtype)
+    if layout not in _LAYOUTS:
+        raise ValueError('layout is "chw" or "hwc"')
+    if not (isinstance(out_w, int) and isinstance(out_h, int) and out_w > 0 and out_h > 0):
+        raise ValueError("out_w and out_h are positive ints")
+    scale3, bias3 = _float3(scale, "scale"), _float3(bias, "bias")
+    nrects = d_x.numel()
+    if d_flip is not None and (d_flip.dtype not in (torch.bool, torch.uint8) or d_flip.numel() != nrects):
+        raise ValueError("d_flip is a bool or uint8 tensor with one entry per crop")
+    if d_out is not None and d_out.dtype != dtype:
+        raise ValueError("d_out is not of the requested dtype")
+    per = 3 * out_w * out_h
+    dev = d_stream.device
+    if d_dst is None:
+        d_dst = torch.arange(nrects, dtype=torch.int64, device=d_x.device) * per
+    if out_cap is None:
+        out_cap = d_out.numel() if d_out is not None else nrects * per
+    d_out = _buffer(d_out, out_cap, dtype, dev, "d_out smaller than out_cap elements", floor=4)
+    if nrects == 0:
+        return d_out, d_dst, (0 if check else None)
+    _check_in_len(d_stream, in_len)
+    _check_offsets(d_offsets, nimg * tiles(w, h))
+    d_rects = torch.stack((d_image, d_x, d_y, d_w, d_h, d_dst), dim=1).contiguous()
+    scratch = _buffer(scratch, crop_resize_scratch_bytes(nrects, max_w, max_h, out_w, out_h), torch.uint8,
+                      dev, "scratch smaller than crop_resize_scratch_bytes(nrects, max_w, max_h, out_w, out_h)",
+                      floor=16)
+    d_result = _buffer(d_result, 3, torch.int64, dev)
+    _call("jpegr_crop_resize_device", d_stream, in_len, w, h, nimg, d_offsets, d_rects, nrects, d_flip,
+          max_w, max_h, out_w, out_h, 1 if antialias else 0, code, _LAYOUTS[layout], scale3, bias3, d_out,
+          out_cap, scratch, d_result, stream_arg(stream))
+    if not check:
+        return d_out, d_dst, None
+    n = _lib.batch_verdict(d_result, stream, JpegError, -1, "jpegr_crop_resize_device: rectangle")
+    return d_out, d_dst, n
+
+
 # -- thumbnails -----------------------------------------------------------------
 def thumb_device(d_stream, in_len, w, h, nimg, first=0, count=None, d_offsets=None, d_out=None,
                  d_dc=None, want_dc=False, scratch=None, d_result=None, stream=None):
@@ -676,6 +733,41 @@ class StreamReader:
             self.crops_tensor(d_image, d_x, d_y, torch.full_like(d_x, w), torch.full_like(d_x, h), w, h,
                               d_dst=d_dst, d_out=d_out, out_cap=d_out.numel(), dtype=dtype,
                               layout=layout, scale=scale, bias=bias, d_flip=d_flip)
+        return d_out.view(shape)
+
+    def crops_resized(self, d_image, d_x, d_y, d_w, d_h, max_w, max_h, out_w, out_h, **kw):
+        """crop_resize_device on this stream: (d_out, d_dst, delivered)."""
+        return crop_resize_device(self.d_stream, self.length, self.w, self.h, self.nimg, self.d_offsets,
+                                  d_image, d_x, d_y, d_w, d_h, max_w, max_h, out_w, out_h, **kw)
+
+    def resized_crop_batch(self, d_image, d_x, d_y, d_w, d_h, out_w, out_h, antialias=True, dtype=None,
+                           layout="chw", mean=None, std=None, d_flip=None, max_w=None, max_h=None):
+        """RandomResizedCrop's batch in one call: crop r is the d_w[r] x d_h[r]
+        pixels from (d_x[r], d_y[r]) of image d_image[r], resampled to
+        out_w x out_h (crop_resize_device: bilinear, antialiased by default),
+        normalised as crop_batch normalises and mirrored where d_flip[r] is
+        not 0.  Returns [n, 3, out_h, out_w] with layout="chw" and
+        [n, out_h, out_w, 3] with "hwc", of `dtype` (default float32).
+        max_w, max_h: bounds on d_w and d_h; the scratch grows with them.  A
+        None costs one read-back, of d_w.max() or d_h.max(), which waits for
+        the device; pass both to keep the call asynchronous apart from its
+        verdict.  No crops: an empty tensor of that shape, without a call."""
+        import torch
+        dtype, _ = _tensor_dtype(dtype)
+        if layout not in _LAYOUTS:
+            raise ValueError('layout is "chw" or "hwc"')
+        if not (isinstance(out_w, int) and isinstance(out_h, int) and out_w > 0 and out_h > 0):
+            raise ValueError("out_w and out_h are positive ints")
+        scale, bias = normalisation(mean, std)
+        n = d_x.numel()
+        shape = (n, 3, out_h, out_w) if layout == "chw" else (n, out_h, out_w, 3)
+        d_out = torch.empty(n * 3 * out_w * out_h, dtype=dtype, device=self.d_stream.device)
+        if n:
+            max_w = int(d_w.max().item()) if max_w is None else max_w
+            max_h = int(d_h.max().item()) if max_h is None else max_h
+            self.crops_resized(d_image, d_x, d_y, d_w, d_h, max_w, max_h, out_w, out_h, antialias=antialias,
+                               d_out=d_out, out_cap=d_out.numel(), dtype=dtype, layout=layout, scale=scale,
+                               bias=bias, d_flip=d_flip)
         return d_out.view(shape)
 
     def thumbnails(self, first=0, count=None):

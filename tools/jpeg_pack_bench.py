@@ -7,7 +7,8 @@ launches.
     python tools/jpeg_pack_bench.py [--steps K] [--once N]
                                     [--decode | --tight [--against LIB] | --direct [--against LIB]
                                      | --crop [--against LIB] | --thumb [--against LIB]
-                                     | --select [--against LIB] | --tensor [--against LIB]]
+                                     | --select [--against LIB] | --tensor [--against LIB]
+                                     | --resize]
 
 Images: bench.py's 3840x2160 random image (synth.rand_rgba_device, seed 1)
 and a 3840x2160 smooth one (tests/test_gpu_entropy.py's generator).  Prints
@@ -107,7 +108,20 @@ alone.  The fused outputs are compared bitwise with the chain's before anything
 is timed.  --against LIB times crop_device of this build and of a second build
 in the same rounds, both by the same bare C call, outputs compared.  All after
 the same pre-warm and settle, alternated over --rounds rounds, event-timed.
-With --once N: N fused calls of each dtype per stream and nothing else."""
+With --once N: N fused calls of each dtype per stream and nothing else.
+
+--resize: crops resampled to one size (jpegr_crop_resize_device), for
+profiles/jpr_resize_bench.md: --tensor's streams; 256 rectangles drawn as
+RandomResizedCrop draws them (area 8 to 100 % of the image, aspect 3/4 to 4/3,
+seeded), each to 224 x 224, ImageNet's normalisation, every second one mirrored.
+The fused call as float32 and as bfloat16 CHW with the TRIANGLE filter; beside
+it, in the same rounds, (a) the chain it replaces: one crops_tensor call with
+float32 CHW packed crops, then per crop interpolate(antialias=True) into the
+batch, the flip, and to(bfloat16); and (b) crop_tensor_device of the same
+rectangles alone, with no resampling, as the floor.  The fused float32 output
+is compared with the chain's before anything is timed: they are not bit-equal
+by design (include/jpegr.h), so the largest |difference| is reported.  With
+--once N: N fused calls of each dtype per stream and nothing else."""
 import argparse
 import json
 import os
@@ -842,6 +856,137 @@ def tensor_side(args, torch, jpeg, synth, dev, other):
             del d_stream
 
 
+def random_resized_rects(rng, n, w, h, nimg):
+    """n rectangles as torchvision's RandomResizedCrop.get_params draws them:
+    area 8 to 100 % of the image, aspect log-uniform in 3/4 .. 4/3, ten tries,
+    then the central crop of the nearest allowed aspect."""
+    out = []
+    for _ in range(n):
+        for _ in range(10):
+            area = w * h * rng.uniform(0.08, 1.0)
+            ar = np.exp(rng.uniform(np.log(3 / 4), np.log(4 / 3)))
+            cw, ch = int(round(np.sqrt(area * ar))), int(round(np.sqrt(area / ar)))
+            if 0 < cw <= w and 0 < ch <= h:
+                x, y = int(rng.integers(0, w - cw + 1)), int(rng.integers(0, h - ch + 1))
+                break
+        else:
+            if w / h < 3 / 4:
+                cw, ch = w, int(round(w / (3 / 4)))
+            elif w / h > 4 / 3:
+                cw, ch = int(round(h * (4 / 3))), h
+            else:
+                cw, ch = w, h
+            x, y = (w - cw) // 2, (h - ch) // 2
+        out.append((int(rng.integers(0, nimg)), x, y, cw, ch))
+    return out
+
+
+def resize_side(args, torch, jpeg, synth, dev):
+    """Crops resampled to one size (jpegr_crop_resize_device) beside the chain it
+    replaces (packed float32 crops, one interpolate a crop) and beside
+    crop_tensor_device of the same rectangles alone."""
+    import torch.nn.functional as F
+    nt = CN * jpeg.tiles(CW, CH)
+    px = CW * CH
+    rects = random_resized_rects(np.random.default_rng(7), NCROPS, CW, CH, CN)
+    t64 = lambda a: torch.from_numpy(np.asarray(a, np.int64)).to(dev)
+    cols = [t64([r[k] for r in rects]) for k in range(5)]
+    mw, mh = max(r[3] for r in rects), max(r[4] for r in rects)
+    sizes = [3 * r[3] * r[4] for r in rects]
+    starts = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    capp, capo = int(starts[-1]), NCROPS * 3 * CROP * CROP
+    d_dstp, d_dsto = t64(starts[:-1]), t64(np.arange(NCROPS) * 3 * CROP * CROP)
+    d_flip = torch.from_numpy((np.arange(NCROPS) % 2).astype(np.uint8)).to(dev)      # half mirrored
+    mask = d_flip.bool().view(NCROPS, 1, 1, 1)
+    scale, bias = jpeg.normalisation(IMAGENET_MEAN, IMAGENET_STD)
+    images = {}
+    d_img = torch.empty(CN * px * 4, dtype=torch.uint8, device=dev)
+    synth.rand_rgba_device(d_img, 0, CN * px, seed=1)
+    images["random"] = d_img
+    images["smooth"] = torch.from_numpy(smooth_image(CW, CH)).to(dev).reshape(-1).repeat(CN)
+    d_offs = torch.empty(nt + 1, dtype=torch.int64, device=dev)
+    d_ires = torch.empty(2, dtype=torch.int64, device=dev)
+    d_res, d_tres = (torch.empty(3, dtype=torch.int64, device=dev) for _ in range(2))
+    iscr = torch.empty(int(jpeg._lib.lib().jpegr_pack_scratch_bytes(nt)), dtype=torch.uint8, device=dev)
+    scr = torch.empty(jpeg.crop_resize_scratch_bytes(NCROPS, mw, mh, CROP, CROP), dtype=torch.uint8, device=dev)
+    d_packed = torch.empty(capp, dtype=torch.float32, device=dev)
+    d_batch = torch.empty(NCROPS, 3, CROP, CROP, dtype=torch.float32, device=dev)
+    d_f32 = torch.empty(capo, dtype=torch.float32, device=dev)
+    d_bf16 = torch.empty(capo, dtype=torch.bfloat16, device=dev)
+    area = sum(r[3] * r[4] for r in rects)
+    for name, img in images.items():
+        for tight in (False, True):
+            d_stream = jpeg.compress_device(img, CW, CH, CN, tight=tight)
+            n = d_stream.numel()
+            jpeg.stream_index_device(d_stream, n, CW, CH, CN, d_offsets=d_offs, d_result=d_ires, scratch=iscr)
+
+            def packed():                                   # (b): no resampling, the crops at source scale
+                jpeg.crop_tensor_device(d_stream, n, CW, CH, CN, d_offs, *cols, mw, mh, d_dst=d_dstp,
+                                        d_out=d_packed, out_cap=capp, scratch=scr, d_result=d_tres,
+                                        check=False, dtype=torch.float32, layout="chw", scale=scale,
+                                        bias=bias)
+
+            def fused(d_out, dtype):
+                jpeg.crop_resize_device(d_stream, n, CW, CH, CN, d_offs, *cols, mw, mh, CROP, CROP,
+                                        antialias=True, d_dst=d_dsto, d_out=d_out, out_cap=capo, scratch=scr,
+                                        d_result=d_res, check=False, dtype=dtype, layout="chw", scale=scale,
+                                        bias=bias, d_flip=d_flip)
+
+            def chain(dtype):                               # (a)
+                packed()
+                for r, (_, _, _, cw, ch) in enumerate(rects):
+                    src = d_packed[int(starts[r]):int(starts[r + 1])].view(1, 3, ch, cw)
+                    d_batch[r:r + 1] = F.interpolate(src, size=(CROP, CROP), mode="bilinear",
+                                                     align_corners=False, antialias=True)
+                t = torch.where(mask, d_batch.flip(3), d_batch)
+                return t if dtype == torch.float32 else t.to(dtype)
+
+            calls = [("resize_f32", lambda: fused(d_f32, torch.float32)),
+                     ("resize_bf16", lambda: fused(d_bf16, torch.bfloat16)),
+                     ("chain_f32", lambda: chain(torch.float32)),
+                     ("chain_bf16", lambda: chain(torch.bfloat16)),
+                     ("packed_f32", packed)]
+            if args.once:
+                for _ in range(args.once):
+                    calls[0][1]()
+                    calls[1][1]()
+                torch.cuda.synchronize()
+                continue
+            calls[0][1]()
+            ok = d_res.cpu().tolist() == [NCROPS, -1, 0]
+            calls[1][1]()
+            ok = ok and d_res.cpu().tolist() == [NCROPS, -1, 0]
+            ref = chain(torch.float32)
+            ok = ok and d_tres.cpu().tolist() == [NCROPS, -1, 0] and d_ires.cpu().tolist() == [n, -1]
+            # the chain normalises before it resamples, the call after: on the
+            # normalised scale, and in bytes (divided by the smallest scale)
+            diff = float((d_f32.view(NCROPS, 3, CROP, CROP) - ref).abs().max().item())
+            res = {"stream": f"{name} {CN} x {CW}x{CH} {'JPT1' if tight else 'JPR1'}",
+                   "crops": f"{NCROPS} RandomResizedCrop rectangles to {CROP}x{CROP}, every second one mirrored",
+                   "max_w": mw, "max_h": mh, "source_pixels": area, "verdicts_ok": ok,
+                   "max_abs_diff_f32_vs_chain": diff, "max_abs_diff_in_bytes": diff / min(scale),
+                   "steps": args.steps, "rounds": args.rounds, "scratch_bytes": scr.numel(),
+                   "packed_f32_bytes": 4 * capp, "out_f32_bytes": 4 * capo}
+            del ref
+            ms = {k: [] for k, _ in calls}
+            for r in range(args.rounds):                  # alternated; the order turns with the round
+                for key, fn in calls[r % len(calls):] + calls[:r % len(calls)]:
+                    settle(fn, torch.cuda.synchronize, chunk=1)
+                    ms[key].append(timed(fn, args.steps, torch))
+            for key, _ in calls:
+                res[key + "_ms"] = spread(ms[key])
+            for d in ("f32", "bf16"):
+                res[f"resize_{d}_over_chain_{d}"] = {
+                    "median": round(res[f"resize_{d}_ms"]["median"] / res[f"chain_{d}_ms"]["median"], 4),
+                    "worst": round(res[f"resize_{d}_ms"]["max"] / res[f"chain_{d}_ms"]["min"], 4)}
+                res[f"resize_{d}_over_packed"] = {
+                    "min": round(min(a / b for a, b in zip(ms[f"resize_{d}"], ms["packed_f32"])), 4),
+                    "median": round(res[f"resize_{d}_ms"]["median"] / res["packed_f32_ms"]["median"], 4),
+                    "max": round(max(a / b for a, b in zip(ms[f"resize_{d}"], ms["packed_f32"])), 4)}
+            print(json.dumps(res), flush=True)
+            del d_stream
+
+
 def thumb_side(args, torch, jpeg, synth, dev, other):
     """Thumbnails straight from the stream beside decode-everything-and-pool."""
     import ctypes
@@ -1124,6 +1269,7 @@ def main():
     ap.add_argument("--thumb", action="store_true")
     ap.add_argument("--select", action="store_true")
     ap.add_argument("--tensor", action="store_true")
+    ap.add_argument("--resize", action="store_true")
     ap.add_argument("--against", default=None,
                     help="with --tight, --direct, --crop, --select or --tensor: a second liblz4jpeg.so to "
                          "alternate with; with --thumb: that, or a second build of jpegr_thumb.hip "
@@ -1134,12 +1280,14 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("jpeg_pack_bench: needs a GPU (there is no CPU path to time)")
     dev = torch.device("cuda:0")
-    if args.crop or args.thumb or args.select or args.tensor:
+    if args.crop or args.thumb or args.select or args.tensor or args.resize:
         if not args.once:                   # clock pre-warm (bench.py run_lz4)
             d_warm = torch.zeros(256 << 20, dtype=torch.uint8, device=dev)
             settle(lambda: d_warm.add_(1), torch.cuda.synchronize, ms=100.0, chunk=16)
             del d_warm
-        if args.tensor:
+        if args.resize:
+            resize_side(args, torch, jpeg, synth, dev)
+        elif args.tensor:
             tensor_side(args, torch, jpeg, synth, dev, second_build(args.against) if args.against else None)
         elif args.crop:
             crop_side(args, torch, jpeg, synth, dev, second_build(args.against) if args.against else None)

@@ -15,8 +15,8 @@
 //                    parse -> sequence records and the block's byte count
 //                    (its LDS layout and primitives: lz4r_tile_lds.h)
 //   lz4r_matches.h   lz4_matches, lz4_window_matches: the batch match finders
-//   lz4r_scan.h      lz4_scan_reduce, lz4_scan_partials: exclusive scan of
-//                    the byte counts
+//   lz4r_scan.h      lz4_scan_reduce16, lz4_scan_partials_frame: exclusive scan
+//                    of the byte counts
 //   lz4r_emit.h      lz4_emit: 32 blocks per workgroup, records -> stream bytes
 //   wave64.h         the wave-level helpers all of them use
 //   lz4r_prof.h      PROF_MARK: nothing in the product, cycle counters or
@@ -26,7 +26,8 @@
 //
 // HBM traffic per input byte: 1 B read + ~0.35 B of records written by
 // lz4_tiles; ~1 B of input + ~0.33 B of record heads read and ~1.03 B
-// written by lz4_emit (+14 B/block of sizes and offsets).
+// written by lz4_emit (+12 B/block: 2 B of size written by lz4_tiles and read
+// by the scan and by lz4_emit, 8 B of offset written).
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -69,11 +70,11 @@ struct lz4r_ctx {
   int device = 0;
   size_t cap_blocks = 0;       // capacity of the per-call per-block arrays
   size_t cap_slots = 0;        // capacity of the slot scratch, in blocks (<= kChunk)
-  uint16_t *bsizes = nullptr;  // encoded bytes of every block of the last call
+  uint16_t *bsizes = nullptr;  // encoded bytes of every block of the last call (what the
+                               // scan and lz4_emit read, and lz4r_copy_block_sizes copies)
   uint64_t *boff = nullptr;    // every block's offset from the first block byte
   uint8_t *slots = nullptr;    // per-block record scratch, one chunk: cap_slots heads of
                                // kHead bytes, then cap_slots overflow slots of kOvf
-  uint32_t *tsz = nullptr;     // encoded bytes per block (u32, for the scan)
   uint32_t *gsum = nullptr;    // encoded bytes per group of kGT blocks
   uint64_t *part = nullptr;    // scan partials, one per kPart blocks
   uint64_t *len = nullptr;     // default device length slot, the status word, the verdict
@@ -100,14 +101,12 @@ namespace {
 void free_scratch(lz4r_ctx *c) {
   (void)hipFree(c->bsizes);
   (void)hipFree(c->boff);
-  (void)hipFree(c->tsz);
   (void)hipFree(c->gsum);
   (void)hipFree(c->part);
   (void)hipFree(c->slots);
   c->bsizes = nullptr;
   c->boff = nullptr;
   c->slots = nullptr;
-  c->tsz = nullptr;
   c->gsum = nullptr;
   c->part = nullptr;
   c->cap_blocks = 0;
@@ -126,7 +125,6 @@ int ensure_scratch(lz4r_ctx *c, size_t nb) {
   if (hipMalloc(&c->slots, cap_slots * (size_t)kSlot) != hipSuccess ||
       hipMalloc(&c->bsizes, cap * sizeof(uint16_t)) != hipSuccess ||
       hipMalloc(&c->boff, cap * sizeof(uint64_t)) != hipSuccess ||
-      hipMalloc(&c->tsz, cap * sizeof(uint32_t)) != hipSuccess ||
       hipMalloc(&c->gsum, groups * sizeof(uint32_t)) != hipSuccess ||
       hipMalloc(&c->part, parts * sizeof(uint64_t)) != hipSuccess) {
     (void)hipGetLastError();
@@ -228,21 +226,28 @@ int run(lz4r_ctx *c, const void *d_in, size_t n, void *d_out, size_t cap,
     // (every chunk starts 300 b0 bytes in: a multiple of 4)
     const auto tiles = ((uintptr_t)in & 3) == 0 ? lz4_tiles<true> : lz4_tiles<false>;
     hipExtLaunchKernelGGL(tiles, dim3(8 * runs), dim3(64), 0, s, t0, t1, 0u, in + b0 * kBlk,
-                          (uint32_t)nbc, per, last_n, c->slots, ovfs, c->tsz + b0,
-                          c->bsizes + b0, c->status);
+                          (uint32_t)nbc, per, last_n, c->slots, ovfs, c->bsizes + b0, c->status);
+    // the chunk's own groups and partials (a chunk starts on a partial)
     const size_t p0 = b0 / kPart, np = (nbc + kPart - 1) / kPart;
-    hipLaunchKernelGGL(lz4_scan_reduce, dim3((unsigned)np), dim3(256), 0, s, c->tsz, b1, p0,
-                       c->gsum, c->part);
-    hipLaunchKernelGGL(lz4_scan_partials, dim3(1), dim3(1024), 0, s, c->part + p0, np,
-                       (uint64_t)hdr, k == 0 ? 1 : 0, k + 1 == nchunks ? 1 : 0, c->status,
-                       static_cast<uint64_t *>(d_len), c->verdict);
     const size_t g0 = b0 / kGT, ng = (nbc + kGT - 1) / kGT;
-    hipExtLaunchKernelGGL(lz4_emit, dim3((unsigned)(8 * ((ng * kGSplit + 7) / 8))), dim3(64 * kEW), 0, s, nullptr,
-                          k + 1 == nchunks ? ev(ts ? ts->c : nullptr) : nullptr, 0u, in,
-                          (const uint8_t *)c->slots, (const uint8_t *)ovfs, b0,
-                          (const uint32_t *)c->tsz, b1, g0, (const uint32_t *)c->gsum,
-                          (const uint64_t *)c->part, static_cast<uint8_t *>(d_out), (uint64_t)cap,
-                          hdr, (uint64_t)nb, (uint32_t)(n - (nb - 1) * kBlk), c->boff);
+    const int frame = hdr && k == 0 && cap > 0 ? (int)(uint8_t)nb : -1;
+    hipLaunchKernelGGL(lz4_scan_reduce16, dim3((unsigned)np), dim3(256), 0, s,
+                       (const uint16_t *)(c->bsizes + b0), (uint32_t)nbc, c->gsum + g0,
+                       c->part + p0);
+    hipLaunchKernelGGL(lz4_scan_partials_frame, dim3(1), dim3(1024), 0, s, c->part + p0, np,
+                       (uint64_t)hdr, k == 0 ? 1 : 0, k + 1 == nchunks ? 1 : 0, c->status,
+                       static_cast<uint64_t *>(d_len), c->verdict, static_cast<uint8_t *>(d_out),
+                       frame);
+    // what every lz4_emit workgroup of the launch shares: the workgroups that
+    // have blocks, and how many of them an XCD takes
+    const uint32_t nwg = (uint32_t)(ng * kGSplit), wper = (nwg + 7) / 8;
+    hipExtLaunchKernelGGL(lz4_emit, dim3(8 * wper), dim3(64 * kEW), 0, s, nullptr,
+                          k + 1 == nchunks ? ev(ts ? ts->c : nullptr) : nullptr, 0u, in + b0 * kBlk,
+                          (const uint8_t *)c->slots, (const uint8_t *)ovfs,
+                          (const uint16_t *)(c->bsizes + b0), (uint32_t)nbc, nwg, wper,
+                          (const uint32_t *)(c->gsum + g0), (const uint64_t *)(c->part + p0),
+                          static_cast<uint8_t *>(d_out), (uint64_t)cap, (uint32_t)hdr, last_n,
+                          c->boff + b0);
   }
   if (timed) ++c->timed_calls;
   c->last_nb = nb;

@@ -103,7 +103,7 @@ __device__ __forceinline__ void emit_records(const int wv, const int lane, const
   // first index
   const uint32_t desc = ns ? ((uint32_t)(lane + 1) << 16) | sst : 0u;
   // the task's blocks are contiguous in the image, each its 3 header bytes
-  // and then its sequences' bytes (tsz counts the bytes written): sequence f
+  // and then its sequences' bytes (bsizes counts the bytes written): sequence f
   // of a round lands at the round's first one + 3 per block start between
   // them + the bytes of the round's sequences before it
   const int rel = lead - (int)(uint32_t)G0;    // image byte = rel + (u32) stream byte
@@ -265,13 +265,19 @@ __device__ __forceinline__ void emit_store(const int tid, const int wv, const in
   }
 }
 
+// Everything per block or per group is the launch chunk's own (in, bsizes, gsum,
+// part, boff point at the chunk's first block, group and partial; ntiles
+// blocks, the last of last_n bytes), and what is the same for every
+// workgroup comes from the host: nwg workgroups with blocks, per of them per
+// XCD.  A chunk has at most 2^24 blocks (lz4r.hip kChunk), so block indices
+// and the heads' byte offsets are 32-bit; the input's and the overflow
+// slots' offsets are not.
 __global__ __launch_bounds__(64 * kEW) void lz4_emit(
     const uint8_t *__restrict__ in, const uint8_t *__restrict__ heads,
-    const uint8_t *__restrict__ ovfs, size_t slot_base,
-    const uint32_t *__restrict__ tsz, size_t ntiles, size_t g_first,
-    const uint32_t *__restrict__ gsum, const uint64_t *__restrict__ part,
-    uint8_t *__restrict__ out, uint64_t cap, int hdr, uint64_t nb_total, uint32_t last_n,
-    uint64_t *__restrict__ boff) {
+    const uint8_t *__restrict__ ovfs, const uint16_t *__restrict__ bsizes, uint32_t ntiles,
+    uint32_t nwg, uint32_t per, const uint32_t *__restrict__ gsum,
+    const uint64_t *__restrict__ part, uint8_t *__restrict__ out, uint64_t cap, uint32_t hdr,
+    uint32_t last_n, uint64_t *__restrict__ boff) {
   __shared__ uint64_t toff[kGT + 1];
   __shared__ alignas(16) uint8_t img[kEmitImg];
   __shared__ alignas(16) uint8_t stage[kStage];
@@ -282,22 +288,20 @@ __global__ __launch_bounds__(64 * kEW) void lz4_emit(
   // XCD-aware order (workgroups b and b + 8 share an XCD): XCD b % 8 takes a
   // contiguous eighth of the workgroups, so neighbouring outputs' boundary
   // lines meet in one L2
-  const uint32_t nwg = (uint32_t)((ntiles - g_first * kGT + kGT - 1) / kGT) * kGSplit;
-  const uint32_t per = (nwg + 7) / 8;
   const uint32_t wg = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
   if (wg >= nwg) return;
-  const size_t g = g_first + wg / kGSplit;
+  const uint32_t g = wg / kGSplit;
   const int h0 = (int)(wg % kGSplit) * kGH;          // this workgroup: blocks [h0, h0 + kGH)
-  const size_t g0 = g * kGT;
-  const int nt = (int)min((size_t)kGT, ntiles - g0);
+  const uint32_t g0 = g * kGT;
+  const int nt = (int)min((uint32_t)kGT, ntiles - g0);
   if (h0 >= nt) return;
   const int h1 = min(nt, h0 + kGH);
   // Every global load of the workgroup is issued before any of them is
   // waited on (the scan inputs, the record heads, the staged input): one
   // memory round trip per workgroup, not three.
-  const size_t b0 = g0 + h0;
-  const int len = (h1 - h0 - 1) * kBlk + (g0 + h1 == nb_total ? (int)last_n : kBlk);
-  const uint8_t *src = in + b0 * kBlk;
+  const uint32_t b0 = g0 + (uint32_t)h0;
+  const int len = (h1 - h0 - 1) * kBlk + (g0 + (uint32_t)h1 == ntiles ? (int)last_n : kBlk);
+  const uint8_t *src = in + (size_t)b0 * kBlk;
   const bool al16 = ((uintptr_t)src & 15) == 0;    // b0 is a multiple of 32: 9600 B steps
   const int n16 = al16 ? len >> 4 : 0;
   uint64_t pt = 0;
@@ -307,19 +311,19 @@ __global__ __launch_bounds__(64 * kEW) void lz4_emit(
     // scan loads, then two wave sums): raised priority until the barrier
     // (emit 0.622 -> 0.603 ms, tools/ab_inproc.py)
     __builtin_amdgcn_s_setprio(3);
-    const size_t p = g0 / kPart;
-    const size_t gfirst = p * 64;                  // first group of the partial
-    gs = (gfirst + tid < g) ? gsum[gfirst + tid] : 0u;
+    const uint32_t p = g0 / kPart;
+    const uint32_t gfirst = p * 64;                // first group of the partial
+    gs = (gfirst + (uint32_t)tid < g) ? gsum[gfirst + (uint32_t)tid] : 0u;
     pt = part[p];                                  // part[] holds absolute offsets
-    tv = tid < nt ? tsz[g0 + tid] : 0u;
+    tv = tid < nt ? (uint32_t)bsizes[g0 + (uint32_t)tid] : 0u;
   }
   constexpr int kPerSlot = kRecPre / 4;            // record heads: 32 x 96 B, contiguous
   static_assert(kGH * kPerSlot <= 64 * kEW, "one record load per thread");
   uint4 rv = make_uint4(0, 0, 0, 0);
   const int rhb = tid / kPerSlot, rj = tid % kPerSlot;
   // the workgroup's heads (one contiguous run) and overflow slots
-  const uint8_t *const wheads = heads + (b0 - slot_base) * (size_t)kHead;
-  const uint8_t *const wovf = ovfs + (b0 - slot_base) * (size_t)kOvf;
+  const uint8_t *const wheads = heads + b0 * (uint32_t)kHead;
+  const uint8_t *const wovf = ovfs + (size_t)b0 * kOvf;
   if (tid < (h1 - h0) * kPerSlot) {
     const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(wheads) + tid);
     rv = make_uint4(t.x, t.y, t.z, t.w);
@@ -348,9 +352,9 @@ __global__ __launch_bounds__(64 * kEW) void lz4_emit(
     if (tid == 63) toff[kGT] = base + inc;
     // device-resident block offsets (relative to the first block byte) for
     // the block-parallel decoder: no host prefix sum, no host round trip
-    if (h0 == 0 && tid < nt) boff[g0 + tid] = base + inc - tv - (uint64_t)hdr;
+    if (h0 == 0 && tid < nt) boff[g0 + (uint32_t)tid] = base + inc - tv - (uint64_t)hdr;
   }
-  if (hdr && g == 0 && h0 == 0 && tid == 0 && cap > 0) out[0] = (uint8_t)nb_total;
+  // (the frame byte out[0] is the scan's: lz4_scan_partials_frame)
   if (tid < (h1 - h0) * kPerSlot) reinterpret_cast<uint4 *>(&recst[rhb][0])[rj] = rv;
   if (tid < 17) {
     uint32_t m[4];

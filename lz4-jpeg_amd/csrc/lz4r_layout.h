@@ -45,7 +45,7 @@ constexpr int kPart = 64 * kGT;      // blocks per scan partial (64 groups)
 static_assert(kPart % kGT == 0, "partials hold whole groups");
 
 // bit 63 of the length word a call leaves: a block saw a corrupt bucket head
-// (set by the call's last lz4_scan_partials, read back by the host)
+// (set by the call's last scan, lz4r_scan.h, read back by the host)
 constexpr uint64_t kLenCorrupt = 1ull << 63;
 
 }  // namespace

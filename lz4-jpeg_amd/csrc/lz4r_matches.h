@@ -23,7 +23,7 @@ __global__ __launch_bounds__(64) void lz4_matches(const uint8_t *__restrict__ in
   RecBatch B;                            // (unused: no records)
   ProfClock prof = PROF_START();
   encode_block<true, false>(S, n, nullptr, K, nullptr, mout + (size_t)t * kBlk, nullptr, nullptr,
-                            nullptr, lane, prof, B, true, nullptr, nullptr, 0u);
+                            nullptr, lane, prof, B, true, nullptr, 0u);
 }
 
 // find_longest_match over a block of any length n (block_encode with a

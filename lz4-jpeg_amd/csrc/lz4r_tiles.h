@@ -81,8 +81,9 @@
 //            takes and of its size fields; the header dword and record k
 //            (lz4r_layout.h) -> the block's record scratch (a dense 96-B
 //            head: header and records 0..22; an overflow slot for the rest);
-//            the block's byte count -> usz (u32, for the scan) and bsizes
-//            (u16).  Two consecutive unstaged blocks of a run share one such
+//            the block's byte count -> bsizes (u16: what the scan and
+//            lz4_emit read, and what the caller is handed).  Two
+//            consecutive unstaged blocks of a run share one such
 //            round, one on each half of the wave (RecBatch, flush_records:
 //            a text block has ~15 sequences); a staged block, or one with
 //            more than 31 match sequences, has a round of its own.
@@ -165,25 +166,22 @@ __device__ __forceinline__ uint32_t half_incl_add(uint32_t v) {
   return v;
 }
 
-// Block tb + lane's header dword = hdr, usz = w, bsizes = (u16) w in the lanes
-// of m, EXEC masked once around the three stores (store_lanes1's way).  The
+// Block tb + lane's header dword = hdr, bsizes = (u16) w in the lanes
+// of m, EXEC masked once around the two stores (store_lanes1's way).  The
 // block index goes into the lanes' 32-bit offsets off the arrays' bases (a
 // launch has at most 2^24 blocks, lz4r.hip kChunk: 96 tb < 2^31); a pointer
 // per array and block cost three SALU each.
 __device__ __forceinline__ void store_block_totals(uint64_t m, uint32_t tb, int lane, uint32_t hdr,
-                                                   uint32_t w, uint8_t *heads, uint32_t *usz,
-                                                   uint16_t *bsizes) {
+                                                   uint32_t w, uint8_t *heads, uint16_t *bsizes) {
   const uint32_t bl = tb + (uint32_t)lane;
   uint64_t save;
   asm volatile(
       "s_and_saveexec_b64 %0, %1\n\t"
-      "global_store_dword %2, %5, %7\n\t"
-      "global_store_dword %3, %6, %8\n\t"
-      "global_store_short %4, %6, %9\n\t"
+      "global_store_dword %2, %4, %6\n\t"
+      "global_store_short %3, %5, %7\n\t"
       "s_or_b64 exec, exec, %0"
       : "=&s"(save)
-      : "s"(m), "v"(bl * (uint32_t)kHead), "v"(bl * 4u), "v"(bl * 2u), "v"(hdr), "v"(w), "s"(heads),
-        "s"(usz), "s"(bsizes)
+      : "s"(m), "v"(bl * (uint32_t)kHead), "v"(bl * 2u), "v"(hdr), "v"(w), "s"(heads), "s"(bsizes)
       : "memory", "scc");
 }
 
@@ -198,7 +196,6 @@ __device__ __forceinline__ void flush_records(const uint32_t wv, const uint32_t 
                                               const uint32_t f1, const uint32_t tb,
                                               uint8_t *__restrict__ heads,
                                               uint8_t *__restrict__ ovfs,
-                                              uint32_t *__restrict__ usz,
                                               uint16_t *__restrict__ bsizes, const int lane) {
   constexpr int n = kBlk;
   const int M = (int)((wv >> 9) & 255u);
@@ -251,7 +248,7 @@ __device__ __forceinline__ void flush_records(const uint32_t wv, const uint32_t 
     store_lanes1(om, reinterpret_cast<uint32_t *>(ovfs + (size_t)tb * kOvf) - kHeadW,
                  x4 + (h32 << 3) + (h32 >> 1), wv);
   static_assert(kOvf - 4 * kHalf == 8 * kHalf + kHalf / 2, "the second overflow slot from lane & 32");
-  store_block_totals(f1 ? 3ull : 1ull, tb, lane, hdr, wb, heads, usz, bsizes);
+  store_block_totals(f1 ? 3ull : 1ull, tb, lane, hdr, wb, heads, bsizes);
 }
 static_assert((128 - kHead) % kHalf == 0 && kHeadW - 1 < kHalf, "the second half's records");
 
@@ -259,7 +256,7 @@ static_assert((128 - kHead) % kHalf == 0 && kHeadW - 1 < kHalf, "the second half
 // bytes staged at S.buf[kInOff]) as sequence records:
 // dwords 0 .. kHeadW - 1 (header, records 0..22) at its head (heads + t kHead),
 // record k >= 23 at dword k + 1 - kHeadW of its overflow slot (ovfs + t kOvf),
-// and the bytes its stream takes at usz[t] / bsizes[t].
+// and the bytes its stream takes at bsizes[t].
 // kMatchesOnly: stop after the best-match scan and store every position's
 // find_longest_match result to mout instead (lz4r_block_matches_device).
 // next (kFull in a run, kTileRun > 1): the block whose dwords are loaded into K
@@ -278,7 +275,6 @@ __device__ __forceinline__ void encode_block(TileLds &S, int n_arg, const uint8_
                                             uint8_t *__restrict__ ovfs,
                                             uint32_t *__restrict__ status, const int lane,
                                             ProfClock &prof, RecBatch &B, const bool flush_after,
-                                            uint32_t *__restrict__ usz,
                                             uint16_t *__restrict__ bsizes, const uint32_t t) {
   // kFull: a whole 300-byte block of a 4-byte aligned input that is not the
   // launch's last (every block but one): n is a constant, only round 4's
@@ -674,9 +670,9 @@ __device__ __forceinline__ void encode_block(TileLds &S, int n_arg, const uint8_
     if (f0) {
       const uint32_t tb = t - (uint32_t)(l0 >> 5);   // the round's first block
       if (slowm == 0u)
-        flush_records<true>(rv, f0, f1, tb, heads, ovfs, usz, bsizes, lane);
+        flush_records<true>(rv, f0, f1, tb, heads, ovfs, bsizes, lane);
       else
-        flush_records<false>(rv, f0, f1, tb, heads, ovfs, usz, bsizes, lane);
+        flush_records<false>(rv, f0, f1, tb, heads, ovfs, bsizes, lane);
     }
     PROF_MARK(6);                     // records (of both blocks of a round)
     if (fits) return;
@@ -790,7 +786,7 @@ __device__ __forceinline__ void encode_block(TileLds &S, int n_arg, const uint8_
   // (no branch on the lane here: where it joined the batched return above,
   // the compiler took the batch state for lane-dependent and kept it in VGPRs)
   store_block_totals(1ull, t, lane, (uint32_t)szsum | ((uint32_t)nseq << 16), (uint32_t)ocar, heads,
-                     usz, bsizes);
+                     bsizes);
 }
 
 // (8 waves per SIMD = 64 VGPRs: around a loop the compiler would otherwise
@@ -798,8 +794,8 @@ __device__ __forceinline__ void encode_block(TileLds &S, int n_arg, const uint8_
 template <bool kAligned>   // the input is 4-byte aligned (the host checks)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void lz4_tiles(
     const uint8_t *__restrict__ in, uint32_t nb, uint32_t per, uint32_t last_n,
-    uint8_t *__restrict__ heads, uint8_t *__restrict__ ovfs, uint32_t *__restrict__ usz,
-    uint16_t *__restrict__ bsizes, uint32_t *__restrict__ status) {
+    uint8_t *__restrict__ heads, uint8_t *__restrict__ ovfs, uint16_t *__restrict__ bsizes,
+    uint32_t *__restrict__ status) {
   __shared__ TileLds S;
   ProfClock prof = PROF_START();
   // XCD-aware order: workgroups w and w + 8 share an XCD (observed round-robin
@@ -842,7 +838,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
       // (not prefetched = no kFull block follows in this run: the pending
       // records leave with this block's)
       encode_block<false, true>(S, kBlk, src, K, pf ? src + kBlk : src, nullptr, heads, ovfs,
-                                status, lane, prof, B, !pf, usz, bsizes, t);
+                                status, lane, prof, B, !pf, bsizes, t);
     } else {
       // the last block (n <= 300: nothing may be read past the input), the one
       // before a last block of < 24 bytes, or an unaligned input: staged
@@ -852,7 +848,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
       wave_sync();
       if (t == t0) PROF_MARK(7);         // wave start .. the first block is staged
       encode_block<false, false>(S, n, nullptr, K, nullptr, nullptr, heads, ovfs, status, lane,
-                                 prof, B, true, usz, bsizes, t);
+                                 prof, B, true, bsizes, t);
     }
     wave_sync();   // the next block's LDS writes stay behind this block's reads
   }

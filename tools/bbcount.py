@@ -247,7 +247,6 @@ def run_emit(outdir, name="prod", nbytes=1 << 30):
     nb = (n + 299) // 300
     last_n = n - (nb - 1) * 300
     slots = torch.empty(nb * (96 + 400), dtype=torch.uint8, device=dev)
-    tsz = torch.empty(nb, dtype=torch.int32, device=dev)
     bsz = torch.empty(nb, dtype=torch.int16, device=dev)
     status = torch.zeros(4, dtype=torch.int64, device=dev)
     npart = (nb + 4095) // 4096
@@ -263,7 +262,7 @@ def run_emit(outdir, name="prod", nbytes=1 << 30):
     S = json.load(open(os.path.join(OUT, f"bb_static_emit_{name}.json")))
     L = open(os.path.join(OUT, f"bbcnt_emit_{name}.s")).read()
     fns = {}
-    for k in ("lz4_tilesILb1EE", "lz4_scan_reduce", "lz4_scan_partials", "lz4_emit"):
+    for k in ("lz4_tilesILb1EE", "lz4_scan_reduce16", "lz4_scan_partials_frame", "lz4_emit"):
         mangled = re.search(r"^(_ZN12_GLOBAL__N_1\d+" + k + r"\S*?):", L, re.M).group(1)
         f = ctypes.c_void_p()
         assert hip.hipModuleGetFunction(ctypes.byref(f), mod, mangled.encode()) == 0, k
@@ -277,16 +276,19 @@ def run_emit(outdir, name="prod", nbytes=1 << 30):
     grid, per = tile_grid(nb)
     heads, ovfs = P(slots), ctypes.c_void_p(slots.data_ptr() + nb * 96)
     _launch(hip, fns["lz4_tilesILb1EE"], grid, 64,
-            [P(d_in), U32(nb), U32(per), U32(last_n), heads, ovfs, P(tsz), P(bsz), P(status)])
-    _launch(hip, fns["lz4_scan_reduce"], npart, 256, [P(tsz), U64(nb), U64(0), P(gsum), P(part)])
+            [P(d_in), U32(nb), U32(per), U32(last_n), heads, ovfs, P(bsz), P(status)])
+    _launch(hip, fns["lz4_scan_reduce16"], npart, 256, [P(bsz), U32(nb), P(gsum), P(part)])
     lenp = ctypes.c_void_p(status.data_ptr() + 8)
     verd = ctypes.c_void_p(status.data_ptr() + 16)
-    _launch(hip, fns["lz4_scan_partials"], 1, 1024,
-            [P(part), U64(npart), U64(1), I32(1), I32(1), P(status), lenp, verd])
+    _launch(hip, fns["lz4_scan_partials_frame"], 1, 1024,
+            [P(part), U64(npart), U64(1), I32(1), I32(1), P(status), lenp, verd, P(out),
+             I32(nb & 255)])
     ng = (nb + 63) // 64
-    _launch(hip, fns["lz4_emit"], ng * 2, 512,
-            [P(d_in), heads, ovfs, U64(0), P(tsz), U64(nb), U64(0), P(gsum), P(part), P(out),
-             U64(cap), I32(1), U64(nb), U32(last_n), P(boff)])
+    nwg = ng * 2
+    wper = (nwg + 7) // 8
+    _launch(hip, fns["lz4_emit"], 8 * wper, 512,
+            [P(d_in), heads, ovfs, P(bsz), U32(nb), U32(nwg), U32(wper), P(gsum), P(part), P(out),
+             U64(cap), U32(1), U32(last_n), P(boff)])
     assert hip.hipDeviceSynchronize() == 0
     host = (ctypes.c_uint32 * NCNT)()
     assert hip.hipMemcpy(host, acc, ctypes.c_size_t(4 * NCNT), 2) == 0
@@ -315,7 +317,6 @@ def run(outdir, name="prod", nbytes=1 << 30):
     assert nb <= 1 << 24
     last_n = n - (nb - 1) * 300
     slots = torch.empty(nb * 640, dtype=torch.uint8, device=dev)
-    usz = torch.empty(nb, dtype=torch.int32, device=dev)
     bsz = torch.empty(nb, dtype=torch.int16, device=dev)
     status = torch.zeros(2, dtype=torch.int32, device=dev)
     torch.cuda.synchronize()
@@ -334,8 +335,7 @@ def run(outdir, name="prod", nbytes=1 << 30):
             ctypes.c_uint32(last_n), ctypes.c_void_p(slots.data_ptr())]
     if "jjjPhS" in kname:             # (heads, overflow slots) since round 5
         args.append(ctypes.c_void_p(slots.data_ptr() + nb * 96))
-    args += [ctypes.c_void_p(usz.data_ptr()), ctypes.c_void_p(bsz.data_ptr()),
-             ctypes.c_void_p(status.data_ptr())]
+    args += [ctypes.c_void_p(bsz.data_ptr()), ctypes.c_void_p(status.data_ptr())]
     params = (ctypes.c_void_p * len(args))(*[ctypes.cast(ctypes.pointer(a), ctypes.c_void_p)
                                               for a in args])
     assert hip.hipModuleLaunchKernel(fn, grid, 1, 1, 64, 1, 1, 0, None, params, None) == 0
@@ -349,7 +349,7 @@ def run(outdir, name="prod", nbytes=1 << 30):
     _, got = comp.compress_device(d_in, n)   # (the product library's result)
     off = comp.block_offsets(nb).astype(np.int64)
     prod = np.diff(np.append(off, got - 1))
-    same = bool((prod == usz.cpu().numpy().astype(np.int64)).all())
+    same = bool((prod == bsz.cpu().numpy().view(np.uint16).astype(np.int64)).all())
     os.makedirs(outdir, exist_ok=True)
     res = {"bytes": n, "blocks": nb, "status": int(status[0].item()),
            "sizes_equal_product": same, "counts": list(host)}

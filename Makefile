@@ -42,7 +42,7 @@ HDRS    := include/lz4r.h include/jpegr.h include/lz4jpeg_compat.h include/lz4jp
            $(CSRC)/lz4r_dec_bare.h $(CSRC)/lz4r_dec_read.h $(CSRC)/jpegr_pack_common.h \
            $(CSRC)/jpegr_entropy_common.h $(CSRC)/jpegr_decode_common.h $(CSRC)/jpegr_crop.h \
            $(CSRC)/jpegr_pixel.h $(CSRC)/jpegr_dct.h $(CSRC)/jpegr_recon.h $(CSRC)/jpegr_tensor_elem.h \
-           $(CSRC)/jpegr_resize.h
+           $(CSRC)/jpegr_resize.h $(CSRC)/jpegr_dataset.h
 OBJS    := $(B)/lz4r.o $(B)/lz4r_gpudec.o $(B)/lz4r_read.o $(B)/jpegr.o $(B)/jpegr_blocks.o \
            $(B)/jpegr_entropy.o $(B)/jpegr_pack.o $(B)/jpegr_stream.o $(B)/jpegr_stream_enc.o \
            $(B)/jpegr_thumb.o $(B)/jpegr_select.o $(B)/jpegr_resize.o \

@@ -548,6 +548,93 @@ int jpegr_crop_resize_device(const void *d_in, size_t in_len, int w, int h, int 
                              void *d_out, size_t out_cap,
                              void *d_scratch, void *d_result, void *stream);
 
+/* A dataset: many streams, each with its own w x h, format and image count,
+ * read by one call.  jpegr_dataset_crop_tensor_device and
+ * jpegr_dataset_crop_resize_device are jpegr_crop_tensor_device and
+ * jpegr_crop_resize_device with d_in, in_len, w, h, nimg and d_tile_offsets
+ * replaced by d_streams and nstreams: a DEVICE array of nstreams
+ * jpegr_stream_desc (8-B aligned; caller memory, read by the call's kernels
+ * and never by the host; nothing is kept on the host).  A descriptor:
+ *   d_in, in_len     the stream on the device, any alignment
+ *   d_tile_offsets   jpegr_stream_index_device's ntiles + 1 u64 for that stream
+ *                    (8-B aligned, untrusted as in the single-stream calls)
+ *   image0           the dataset-wide index of the stream's image 0
+ *   w, h, nimg       the stream's dimensions; reserved is ignored
+ * jpegr_rect is unchanged; its `image` is a dataset-wide index g.  Rectangle r
+ * belongs to the stream s with image0[s] <= g < image0[s] + nimg[s] and is
+ * image g - image0[s] of it.  Callers build the table ascending in image0 and
+ * gap-free (image0[s + 1] = image0[s] + nimg[s]).  The call's first launch
+ * finds s by bisection over image0, a lane a rectangle, and then tests the
+ * containment: an index no stream contains is a bad rectangle, and with a table
+ * that is not ascending a rectangle is either delivered from a stream that does
+ * contain its index or bad.
+ * Values: a good rectangle's elements are bit for bit what
+ * jpegr_crop_tensor_device (jpegr_crop_resize_device) writes for the same
+ * rectangle, with image = g - image0[s], on stream s alone; dst, d_flip, dtype,
+ * layout, scale3, bias3, filter, out_w and out_h mean what they mean there, and
+ * the value sections above are the contract.
+ * Good, bad, empty: the single-stream calls' rules, each judged against the
+ * rectangle's OWN stream: x + w, y + h and the image index against that
+ * descriptor's w, h and nimg, and the stream's 16 header bytes must be a JPR1 or
+ * JPT1 header for the descriptor's w, h, nimg.  max_w and max_h bound every
+ * rectangle; they are not compared with any stream's size (the host never reads
+ * the table), so a max_w wider than some stream is no error.  A descriptor makes
+ * every rectangle of its stream bad, and only those, when w, h or nimg is 0;
+ * the stream has more than 2^32 tiles; in_len < 16; d_in or d_tile_offsets is
+ * NULL or d_tile_offsets is not 8-B aligned; or the header is wrong.  A tile
+ * with bad offsets, a rejected record or a rejected entropy stream turns bad
+ * only the rectangles that touch it.  Good rectangles are exact whatever bad
+ * rectangles, bad descriptors and other streams do.  The tensor call keeps
+ * "w == 0 or h == 0 is good and writes nothing" for a rectangle whose stream is
+ * found and sound; in the resize call such a rectangle is bad.
+ * d_result: the three words of the single-stream calls; [0] and [2] count over
+ * all streams, [1] is ~0 or 1 + the index of the first bad rectangle.
+ * The scratch: jpegr_dataset_crop_scratch_bytes(nrects, max_w, max_h) or
+ * jpegr_dataset_crop_resize_scratch_bytes(nrects, max_w, max_h, out_w, out_h)
+ * bytes, 16-B aligned: the single-stream call's scratch and one u64 per
+ * rectangle (stream << 32 | image in the stream) that the first launch hands to
+ * the decode.  Both return 0 on a bad argument or a size past SIZE_MAX, are
+ * monotone in nrects and never below their single-stream counterparts.
+ * Whatever the table, the streams, the offsets and the rectangles say, no read
+ * leaves d_streams[0, nstreams), each descriptor's d_in[0, in_len) and
+ * d_tile_offsets[0, ntiles] (ntiles from the descriptor's w, h, nimg),
+ * d_rects[0, nrects) and d_flip[0, nrects): the pointers in a descriptor are
+ * trusted to cover those ranges, nothing else in it is trusted.  Writes are
+ * limited as in the single-stream calls.
+ * Asynchronous on `stream`, no host read-back, no host state: capturable and
+ * replayable, several calls in flight, each with its own scratch and result.
+ * The launches are the single-stream calls' (three and five), with the first
+ * two replaced by their dataset forms.  JPEGR_ERR_ARG before any HIP call:
+ * everything the single-stream call rejects that does not need a stream's
+ * dimensions (a NULL d_rects, d_out, d_scratch or d_result; nrects, max_w or
+ * max_h of 0; the alignments; nrects * K > 2^28; dtype, layout, filter, out_w,
+ * out_h, scale3, bias3), and nstreams == 0 or > 2^31, and a NULL or misaligned
+ * d_streams. */
+typedef struct jpegr_stream_desc {
+  const void *d_in;            /* the stream, device */
+  uint64_t    in_len;
+  const void *d_tile_offsets;  /* jpegr_stream_index_device's, ntiles + 1 u64 */
+  uint64_t    image0;          /* dataset-wide index of this stream's image 0 */
+  uint32_t    w, h, nimg, reserved;
+} jpegr_stream_desc;           /* 48 B */
+
+size_t jpegr_dataset_crop_scratch_bytes(size_t nrects, int max_w, int max_h);
+size_t jpegr_dataset_crop_resize_scratch_bytes(size_t nrects, int max_w, int max_h,
+                                               int out_w, int out_h);
+int jpegr_dataset_crop_tensor_device(const void *d_streams, size_t nstreams,
+                                     const void *d_rects, size_t nrects,
+                                     const void *d_flip, int max_w, int max_h,
+                                     int dtype, int layout, const float *scale3, const float *bias3,
+                                     void *d_out, size_t out_cap,
+                                     void *d_scratch, void *d_result, void *stream);
+int jpegr_dataset_crop_resize_device(const void *d_streams, size_t nstreams,
+                                     const void *d_rects, size_t nrects,
+                                     const void *d_flip, int max_w, int max_h,
+                                     int out_w, int out_h, int filter,
+                                     int dtype, int layout, const float *scale3, const float *bias3,
+                                     void *d_out, size_t out_cap,
+                                     void *d_scratch, void *d_result, void *stream);
+
 /* Thumbnails: images [image0, image0 + nimage) of a JPR1 or JPT1 stream at 1/8
  * scale, one RGBA8 pixel per tile, from the tiles' DC terms alone.  With
  * gw = ceil(w / 8) and gh = ceil(h / 8), pixel (tx, ty) of an image's

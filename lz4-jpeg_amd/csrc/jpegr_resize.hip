@@ -7,6 +7,9 @@
 //                 shadow jpegr_rect, whose dst is its slot of RGBA8 pixels in
 //                 the scratch.  jprs_crop_decode and jpeg_crop_recon_kernel then
 //                 run on the shadows as they are.
+//   jprs_dataset_crop_resize_init   the same for
+//                 jpegr_dataset_crop_resize_device: the rectangle's stream found
+//                 in the table of descriptors first (jpegr_dataset.h)
 //   jpeg_resize_weights     a thread per (rectangle, axis, output index): the
 //                 window and its weights in fp64 by the header's text, each
 //                 weight rounded once to fp32.  Once per tap, not per pixel.
@@ -30,6 +33,7 @@
 
 #include "../../include/jpegr.h"
 #include "jpegr_crop.h"
+#include "jpegr_dataset.h"
 #include "jpegr_pack_common.h"
 #include "jpegr_resize.h"
 #include "jpegr_tensor_elem.h"
@@ -67,6 +71,43 @@ __global__ __launch_bounds__(256) void jprs_crop_resize_init(
   }
   shadow[r] = sh;
   status[r] = st;
+}
+
+// jprs_crop_resize_init over a dataset (jpegr_dataset.h): the rectangle's
+// stream by bisection, the same rules against that stream's own w, h and nimg,
+// the shadow, and the word jprs_dataset_crop_decode finds the stream by.  (Its
+// own text: jprs_crop_resize_init stays the code it was.)
+__global__ __launch_bounds__(256) void jprs_dataset_crop_resize_init(
+    const jpegr_stream_desc *__restrict__ ds, uint64_t nstreams, const jpegr_rect *__restrict__ rects,
+    size_t nrects, size_t r_base, uint32_t max_w, uint32_t max_h, uint64_t elems, uint64_t out_cap,
+    uint64_t pix_slot, jpegr_rect *__restrict__ shadow, uint32_t *__restrict__ status,
+    uint64_t *__restrict__ where, uint64_t *__restrict__ result) {
+  const size_t r = r_base + (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (r == 0) {
+    result[0] = 0ull;
+    result[1] = ~0ull;
+    result[2] = 0ull;
+  }
+  if (r >= nrects) return;
+  const jpegr_rect rc = rects[r];
+  jpegr_stream_desc d;
+  uint32_t s = 0, image = 0;
+  uint32_t st = jpegr_crop::kGood;
+  if (!jpegr_dataset::stream_of_image(ds, nstreams, rc.image, d, s, image) || rc.w == 0 || rc.h == 0 ||
+      rc.w > max_w || rc.h > max_h || rc.x > d.w || rc.w > d.w - rc.x || rc.y > d.h || rc.h > d.h - rc.y ||
+      rc.dst > out_cap || elems > out_cap - rc.dst)
+    st = jpegr_crop::kBad;
+  // a bad rectangle's shadow and word are never read past its status; they hold zeros
+  jpegr_rect sh = {0, 0, 0, 0, 0, 0};
+  uint64_t wh = 0;
+  if (st == jpegr_crop::kGood) {
+    sh = rc;
+    sh.dst = (uint64_t)r * pix_slot;
+    wh = jpegr_dataset::word_of(s, image);
+  }
+  shadow[r] = sh;
+  status[r] = st;
+  where[r] = wh;
 }
 
 // Entry e of the call: output index k of rectangle e / (out_w + out_h), the x
@@ -228,6 +269,22 @@ void jpegr_resize_init_launch(const uint8_t *d_in, size_t in_len, size_t ntiles,
   });
 }
 
+void jpegr_dataset_resize_init_launch(const jpegr_stream_desc *d_streams, size_t nstreams,
+                                      const jpegr_rect *d_rects, size_t nrects, int max_w, int max_h,
+                                      int out_w, int out_h, size_t out_cap, const jpegr_resize::Layout &L,
+                                      void *d_scratch, uint64_t *d_result, hipStream_t st) {
+  auto *base = static_cast<uint8_t *>(d_scratch);
+  auto *shadow = reinterpret_cast<jpegr_rect *>(base + L.shadow);
+  auto *status = reinterpret_cast<uint32_t *>(base + L.status);
+  auto *where = reinterpret_cast<uint64_t *>(base + L.bytes);     // behind the single-stream call's scratch
+  const uint64_t elems = 3ull * (uint64_t)out_w * (uint64_t)out_h;
+  launch_chunks(nrects, 256, [&](size_t b, unsigned n) {
+    hipLaunchKernelGGL(jprs_dataset_crop_resize_init, dim3(n), dim3(256), 0, st, d_streams,
+                       (uint64_t)nstreams, d_rects, nrects, b * 256, (uint32_t)max_w, (uint32_t)max_h, elems,
+                       (uint64_t)out_cap, (uint64_t)L.pix_slot, shadow, status, where, d_result);
+  });
+}
+
 int jpegr_resize_launch(const jpegr_resize::Layout &L, void *d_scratch, const jpegr_rect *d_rects,
                         size_t nrects, int out_w, int out_h, int filter, const uint8_t *d_flip, int dtype,
                         int layout, const float *scale3, const float *bias3, void *d_out, hipStream_t st) {
@@ -259,4 +316,11 @@ extern "C" size_t jpegr_crop_resize_scratch_bytes(size_t nrects, int max_w, int 
                                                   int out_h) {
   jpegr_resize::Layout L;
   return jpegr_resize::layout_of(nrects, max_w, max_h, out_w, out_h, L) ? L.bytes : 0;
+}
+
+extern "C" size_t jpegr_dataset_crop_resize_scratch_bytes(size_t nrects, int max_w, int max_h, int out_w,
+                                                          int out_h) {
+  jpegr_resize::Layout L;
+  if (!jpegr_resize::layout_of(nrects, max_w, max_h, out_w, out_h, L)) return 0;
+  return jpegr_dataset::scratch_with_words(L.bytes, nrects);
 }

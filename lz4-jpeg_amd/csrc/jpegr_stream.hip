@@ -39,6 +39,12 @@
 //                 (jpegr_resize.h); between them jprs_crop_decode and
 //                 jpeg_crop_recon_kernel as they are, on shadow rectangles
 //                 whose pixels go to the scratch; DESIGN 4.17
+//   jpegr_dataset_crop_tensor_device, jpegr_dataset_crop_resize_device are
+//                 those two calls over many streams of different sizes and
+//                 formats (jpegr_dataset.h): jprs_dataset_crop_tensor_init (or
+//                 jpegr_resize.hip's dataset init) finds each rectangle's
+//                 stream, jprs_dataset_crop_decode decodes lanes of both
+//                 formats in one wave; the rest as it is; DESIGN 4.18
 //
 // The per-stream walk is the slot decoder's (jpegr_decode_common.h:
 // decode_stream / decode_stream_slow, the decode state, the carry-chain
@@ -52,6 +58,7 @@
 
 #include "../../include/jpegr.h"
 #include "jpegr_crop.h"
+#include "jpegr_dataset.h"
 #include "jpegr_decode_common.h"
 #include "jpegr_pack_common.h"
 #include "jpegr_resize.h"
@@ -389,6 +396,90 @@ __global__ __launch_bounds__(2 * kLanes) void jprs_crop_decode(
   else
     decode_record<false>(SY, SC, lane, wv, rec, size, t, CropReport{result, stat}, tile_out);
 }
+
+// ---- crops from many streams (jpegr_dataset_crop_*_device; jpegr_dataset.h) --------
+
+// jprs_crop_tensor_init over a dataset: the rectangle's stream by bisection
+// (stream_of_image, which also judges the descriptor and its header), then
+// jprs_crop_tensor_init's rules against that stream's own w, h and nimg, and
+// the word the decode finds the stream by.  (Its own text: the single-stream
+// kernels stay the code they were.)
+__global__ __launch_bounds__(256) void jprs_dataset_crop_tensor_init(
+    const jpegr_stream_desc *__restrict__ ds, uint64_t nstreams, const jpegr_rect *__restrict__ rects,
+    size_t nrects, size_t r_base, uint32_t max_w, uint32_t max_h, uint64_t out_cap,
+    uint32_t *__restrict__ status, uint64_t *__restrict__ where, uint64_t *__restrict__ result) {
+  const size_t r = r_base + (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (r == 0) {
+    result[0] = 0ull;
+    result[1] = ~0ull;
+    result[2] = 0ull;
+  }
+  if (r >= nrects) return;
+  const jpegr_rect rc = rects[r];
+  jpegr_stream_desc d;
+  uint32_t s = 0, image = 0;
+  uint32_t st = jpegr_crop::kGood;
+  if (!jpegr_dataset::stream_of_image(ds, nstreams, rc.image, d, s, image))
+    st = jpegr_crop::kBad;
+  else if (rc.w == 0 || rc.h == 0)
+    st = jpegr_crop::kEmpty;
+  else if (rc.w > max_w || rc.h > max_h || rc.x > d.w || rc.w > d.w - rc.x || rc.y > d.h ||
+           rc.h > d.h - rc.y || rc.dst > out_cap ||
+           3 * rc.w * rc.h > out_cap - rc.dst)         // w <= max_w, h <= max_h < 2^31: no wrap
+    st = jpegr_crop::kBad;
+  status[r] = st;
+  where[r] = jpegr_dataset::word_of(s, image);         // read for a good rectangle only
+}
+
+// jprs_crop_decode over a dataset: the same items, a luma wave and a chroma
+// wave; a lane takes the stream, its length, its tile grid and its offsets from
+// the descriptor its rectangle's word names (s < nstreams: the init kernel
+// stored it for every good rectangle, and no other is read).  A workgroup's 64
+// items span several rectangles, so the format is the lane's and no longer the
+// launch's: a wave runs decode_record<true> on its JPT1 lanes, then
+// decode_record<false> on its JPR1 lanes, and skips by ballot the one no lane
+// needs.  decode_record and what it calls use the wave's active lanes only
+// (ballots over them, a lane's own LDS column, atomics), as they already do
+// behind jprs_crop_decode's idle cells and bad rectangles.
+__global__ __launch_bounds__(2 * kLanes) void jprs_dataset_crop_decode(
+    const jpegr_stream_desc *__restrict__ ds, const uint64_t *__restrict__ where,
+    const jpegr_rect *__restrict__ rects, size_t nrects, uint32_t K, size_t wg_base, uint32_t *status,
+    uint64_t *__restrict__ result, int16_t *__restrict__ coef) {
+  __shared__ DecLds<64, kFastCap> SY;
+  __shared__ DecLds<32, kChromaCap> SC;
+  const int tid = threadIdx.x, lane = tid & (kLanes - 1), wv = tid >> 6;
+  const size_t i = (wg_base + blockIdx.x) * kLanes + lane;
+  const size_t r = i / K;
+  if (r >= nrects) return;
+  const uint32_t cell = (uint32_t)(i - r * K);
+  uint32_t *const stat = status + r;
+  if (*stat != jpegr_crop::kGood) return;            // bad on its own fields or its stream, empty, or a tile failed
+  const jpegr_rect rc = rects[r];
+  const jpegr_crop::Grid g = jpegr_crop::grid_of(rc);
+  if ((uint64_t)cell >= (uint64_t)g.gw * g.gh) return;   // an idle cell
+  const uint32_t cy = cell / g.gw, cx = cell - cy * g.gw;
+  const uint64_t wh = where[r];
+  const jpegr_stream_desc d = ds[wh >> 32];
+  const uint32_t tiles_x = jpegr_dataset::tiles_across(d.w), tiles_y = jpegr_dataset::tiles_across(d.h);
+  // inside the image (the init kernel): t < ntiles <= 2^32, so toff[t + 1] is the caller's
+  const size_t t = ((size_t)(uint32_t)wh * tiles_y + g.ty0 + cy) * tiles_x + g.tx0 + cx;
+  const uint8_t *const in = static_cast<const uint8_t *>(d.d_in);
+  uint64_t o0;
+  uint32_t size;
+  if (!record_at(static_cast<const uint64_t *>(d.d_tile_offsets), t, d.in_len, o0, size)) {
+    if (wv == 0) CropReport{result, stat}.malformed(t);
+    return;
+  }
+  const uint8_t *rec = in + o0;
+  int16_t *const tile_out = coef + i * 128;
+  const bool tight = in[2] == 'T';                    // 'R' or 'T': the header the init kernel accepted
+  if (__ballot(tight) != 0) {
+    if (tight) decode_record<true>(SY, SC, lane, wv, rec, size, t, CropReport{result, stat}, tile_out);
+  }
+  if (__ballot(!tight) != 0) {
+    if (!tight) decode_record<false>(SY, SC, lane, wv, rec, size, t, CropReport{result, stat}, tile_out);
+  }
+}
 }  // namespace
 
 extern "C" int jpegr_stream_decode_device(const void *d_in, size_t in_len, int w, int h, int nimg,
@@ -551,6 +642,103 @@ extern "C" int jpegr_crop_resize_device(const void *d_in, size_t in_len, int w, 
                        static_cast<const uint64_t *>(d_tile_offsets), shadow, nrects, (uint32_t)K, b,
                        status, result, coef);
   });
+  if (jpegr_crop_recon_launch(coef, status, shadow, nrects, max_w, max_h, base + L.pix, result, st) !=
+      JPEGR_OK)
+    return JPEGR_ERR_HIP;
+  return jpegr_resize_launch(L, d_scratch, rects, nrects, out_w, out_h, filter,
+                             static_cast<const uint8_t *>(d_flip), dtype, layout, scale3, bias3, d_out, st);
+}
+
+// ---- the dataset calls ------------------------------------------------
+
+extern "C" size_t jpegr_dataset_crop_scratch_bytes(size_t nrects, int max_w, int max_h) {
+  return jpegr_dataset::scratch_with_words(jpegr_crop_scratch_bytes(nrects, max_w, max_h), nrects);
+}
+
+// what both dataset calls reject of the table, before any HIP call
+static bool bad_table(const void *d_streams, size_t nstreams) {
+  return !d_streams || nstreams == 0 || nstreams > jpegr_dataset::kMaxStreams || misaligned(d_streams, 7);
+}
+
+// the dataset calls' second launch: jprs_crop_decode's items over `rects`
+static void dataset_decode_launch(const jpegr_stream_desc *ds, const uint64_t *where, const jpegr_rect *rects,
+                                  size_t nrects, size_t K, uint32_t *status, uint64_t *result,
+                                  int16_t *coef, hipStream_t st) {
+  launch_chunks(nrects * K, kLanes, [&](size_t b, unsigned n) {
+    hipLaunchKernelGGL(jprs_dataset_crop_decode, dim3(n), dim3(2 * kLanes), 0, st, ds, where, rects, nrects,
+                       (uint32_t)K, b, status, result, coef);
+  });
+}
+
+extern "C" int jpegr_dataset_crop_tensor_device(const void *d_streams, size_t nstreams,
+                                                const void *d_rects, size_t nrects, const void *d_flip,
+                                                int max_w, int max_h, int dtype, int layout,
+                                                const float *scale3, const float *bias3, void *d_out,
+                                                size_t out_cap, void *d_scratch, void *d_result,
+                                                void *stream) {
+  const size_t K = jpegr_crop_items(max_w, max_h);
+  if (bad_table(d_streams, nstreams) || !d_rects || !d_out || !d_scratch || !d_result || nrects == 0 ||
+      K == 0 || misaligned(d_rects, 7) || misaligned(d_result, 7) || misaligned(d_scratch, 15) ||
+      misaligned(d_out, 15) || dtype < JPEGR_DTYPE_U8 || dtype > JPEGR_DTYPE_BF16 ||
+      (layout != JPEGR_LAYOUT_CHW && layout != JPEGR_LAYOUT_HWC) ||
+      nrects > kMaxWg * kLanes / K)                   // one launch_chunks pass: 2^28 items
+    return JPEGR_ERR_ARG;
+  for (int c = 0; c < 3; ++c)
+    if ((scale3 && !isfinite(scale3[c])) || (bias3 && !isfinite(bias3[c]))) return JPEGR_ERR_ARG;
+  const size_t crop = jpegr_crop_scratch_bytes(nrects, max_w, max_h);
+  if (jpegr_dataset::scratch_with_words(crop, nrects) == 0) return JPEGR_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  auto *ds = static_cast<const jpegr_stream_desc *>(d_streams);
+  auto *rects = static_cast<const jpegr_rect *>(d_rects);
+  auto *result = static_cast<uint64_t *>(d_result);
+  auto *base = static_cast<uint8_t *>(d_scratch);
+  auto *coef = static_cast<int16_t *>(d_scratch);
+  auto *status = reinterpret_cast<uint32_t *>(base + nrects * K * 256);
+  auto *where = reinterpret_cast<uint64_t *>(base + crop);
+  launch_chunks(nrects, 256, [&](size_t b, unsigned n) {
+    hipLaunchKernelGGL(jprs_dataset_crop_tensor_init, dim3(n), dim3(256), 0, st, ds, (uint64_t)nstreams,
+                       rects, nrects, b * 256, (uint32_t)max_w, (uint32_t)max_h, (uint64_t)out_cap, status,
+                       where, result);
+  });
+  dataset_decode_launch(ds, where, rects, nrects, K, status, result, coef, st);
+  return jpegr_crop_tensor_launch(coef, status, rects, nrects, max_w, max_h,
+                                  static_cast<const uint8_t *>(d_flip), dtype, layout, scale3, bias3,
+                                  d_out, result, st);
+}
+
+extern "C" int jpegr_dataset_crop_resize_device(const void *d_streams, size_t nstreams,
+                                                const void *d_rects, size_t nrects, const void *d_flip,
+                                                int max_w, int max_h, int out_w, int out_h, int filter,
+                                                int dtype, int layout, const float *scale3,
+                                                const float *bias3, void *d_out, size_t out_cap,
+                                                void *d_scratch, void *d_result, void *stream) {
+  const size_t K = jpegr_crop_items(max_w, max_h);
+  if (bad_table(d_streams, nstreams) || !d_rects || !d_out || !d_scratch || !d_result || nrects == 0 ||
+      K == 0 || misaligned(d_rects, 7) || misaligned(d_result, 7) || misaligned(d_scratch, 15) ||
+      misaligned(d_out, 15) || dtype < JPEGR_DTYPE_U8 || dtype > JPEGR_DTYPE_BF16 ||
+      (layout != JPEGR_LAYOUT_CHW && layout != JPEGR_LAYOUT_HWC) ||
+      (filter != JPEGR_FILTER_BILINEAR && filter != JPEGR_FILTER_TRIANGLE) || out_w <= 0 || out_h <= 0 ||
+      (long long)out_w * out_h > 0x7fffffffll / 3 ||  // a rectangle's 3 out_w out_h elements fit an int
+      nrects > kMaxWg * kLanes / K)                   // one launch_chunks pass: 2^28 items
+    return JPEGR_ERR_ARG;
+  for (int c = 0; c < 3; ++c)
+    if ((scale3 && !isfinite(scale3[c])) || (bias3 && !isfinite(bias3[c]))) return JPEGR_ERR_ARG;
+  jpegr_resize::Layout L;
+  if (!jpegr_resize::layout_of(nrects, max_w, max_h, out_w, out_h, L) ||
+      jpegr_dataset::scratch_with_words(L.bytes, nrects) == 0)
+    return JPEGR_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  auto *ds = static_cast<const jpegr_stream_desc *>(d_streams);
+  auto *rects = static_cast<const jpegr_rect *>(d_rects);
+  auto *result = static_cast<uint64_t *>(d_result);
+  auto *base = static_cast<uint8_t *>(d_scratch);
+  auto *coef = static_cast<int16_t *>(d_scratch);
+  auto *status = reinterpret_cast<uint32_t *>(base + L.status);
+  auto *shadow = reinterpret_cast<const jpegr_rect *>(base + L.shadow);
+  auto *where = reinterpret_cast<const uint64_t *>(base + L.bytes);
+  jpegr_dataset_resize_init_launch(ds, nstreams, rects, nrects, max_w, max_h, out_w, out_h, out_cap, L,
+                                   d_scratch, result, st);
+  dataset_decode_launch(ds, where, shadow, nrects, K, status, result, coef, st);
   if (jpegr_crop_recon_launch(coef, status, shadow, nrects, max_w, max_h, base + L.pix, result, st) !=
       JPEGR_OK)
     return JPEGR_ERR_HIP;

@@ -81,6 +81,14 @@ SIGNATURES = [
     ("jpegr_crop_resize_device", _i, [_vp, _c_size, _i, _i, _i, _vp, _vp, _c_size, _vp, _i, _i, _i, _i, _i,
                                       _i, _i, ctypes.POINTER(ctypes.c_float),
                                       ctypes.POINTER(ctypes.c_float), _vp, _c_size, _vp, _vp, _vp]),
+    ("jpegr_dataset_crop_scratch_bytes", _c_size, [_c_size, _i, _i]),
+    ("jpegr_dataset_crop_resize_scratch_bytes", _c_size, [_c_size, _i, _i, _i, _i]),
+    ("jpegr_dataset_crop_tensor_device", _i, [_vp, _c_size, _vp, _c_size, _vp, _i, _i, _i, _i,
+                                              ctypes.POINTER(ctypes.c_float),
+                                              ctypes.POINTER(ctypes.c_float), _vp, _c_size, _vp, _vp, _vp]),
+    ("jpegr_dataset_crop_resize_device", _i, [_vp, _c_size, _vp, _c_size, _vp, _i, _i, _i, _i, _i, _i, _i,
+                                              ctypes.POINTER(ctypes.c_float),
+                                              ctypes.POINTER(ctypes.c_float), _vp, _c_size, _vp, _vp, _vp]),
     ("jpegr_thumb_scratch_bytes", _c_size, [_c_size]),
     ("jpegr_thumb_device", _i, [_vp, _c_size, _i, _i, _i, _vp, _c_size, _c_size, _vp, _vp, _vp, _vp,
                                 _vp]),

@@ -530,6 +530,131 @@ def crop_resize_device(d_stream, in_len, w, h, nimg, d_offsets, d_image, d_x, d_
     return d_out, d_dst, n
 
 
+# -- crops from many streams ------------------------------------------------------
+STREAM_DESC_BYTES = 48                    # sizeof(jpegr_stream_desc)
+
+
+def stream_table(rows):
+    """jpegr_stream_desc's bytes on the host: rows of (d_in, in_len,
+    d_tile_offsets, image0, w, h, nimg) -- the two pointers as addresses -- to a
+    uint64 array [n, 6]: the four 8-B fields, then w | h << 32 and nimg (the
+    reserved word 0)."""
+    rows = [tuple(int(v) for v in r) for r in rows]
+    if any(len(r) != 7 for r in rows):
+        raise ValueError("a row is (d_in, in_len, d_tile_offsets, image0, w, h, nimg)")
+    if any(not 0 <= v < 1 << 32 for r in rows for v in r[4:]):
+        raise ValueError("w, h and nimg are 32-bit")
+    table = np.array([[p, n, o, i0, w | h << 32, nimg] for p, n, o, i0, w, h, nimg in rows], np.uint64)
+    return table.reshape(len(rows), 6)
+
+
+def dataset_crop_scratch_bytes(nrects, max_w, max_h):
+    return int(_lib.call("jpegr_dataset_crop_scratch_bytes", nrects, max_w, max_h))
+
+
+def dataset_crop_resize_scratch_bytes(nrects, max_w, max_h, out_w, out_h):
+    return int(_lib.call("jpegr_dataset_crop_resize_scratch_bytes", nrects, max_w, max_h, out_w, out_h))
+
+
+def _check_table(d_streams, nstreams):
+    if nstreams <= 0 or d_streams.numel() * d_streams.element_size() < nstreams * STREAM_DESC_BYTES:
+        raise ValueError("d_streams smaller than nstreams descriptors, or none")
+
+
+def dataset_crop_tensor_device(d_streams, nstreams, d_image, d_x, d_y, d_w, d_h, max_w, max_h, d_dst=None,
+                               d_out=None, out_cap=None, scratch=None, d_result=None, stream=None,
+                               check=True, dtype=None, layout="chw", scale=None, bias=None, d_flip=None):
+    """crop_tensor_device over many streams in one call
+    (jpegr_dataset_crop_tensor_device): d_streams is a device tensor holding
+    nstreams jpegr_stream_desc (stream_table's rows; the streams and offsets
+    they point to are the caller's to keep alive), d_image a dataset-wide image
+    index, and every rectangle is judged against its own stream's size.  max_w
+    and max_h bound the rectangles only.  The scratch is
+    dataset_crop_scratch_bytes(nrects, max_w, max_h) bytes.  Everything else,
+    the returns and check=False included, is crop_tensor_device's."""
+    import torch
+    dtype, code = _tensor_dtype(dtype)
+    if layout not in _LAYOUTS:
+        raise ValueError('layout is "chw" or "hwc"')
+    scale3, bias3 = _float3(scale, "scale"), _float3(bias, "bias")
+    nrects = d_x.numel()
+    if d_flip is not None and (d_flip.dtype not in (torch.bool, torch.uint8) or d_flip.numel() != nrects):
+        raise ValueError("d_flip is a bool or uint8 tensor with one entry per crop")
+    if d_out is not None and d_out.dtype != dtype:
+        raise ValueError("d_out is not of the requested dtype")
+    if d_dst is None:
+        d_len = 3 * d_w * d_h
+        d_dst = torch.cumsum(d_len, 0) - d_len
+    if out_cap is None:
+        if d_out is not None:
+            out_cap = d_out.numel()
+        elif check and nrects:
+            out_cap = int((d_dst + 3 * d_w * d_h).max().item())
+        else:
+            out_cap = nrects * 3 * max_w * max_h
+    dev = d_streams.device
+    d_out = _buffer(d_out, out_cap, dtype, dev, "d_out smaller than out_cap elements", floor=4)
+    if nrects == 0:
+        return d_out, d_dst, (0 if check else None)
+    _check_table(d_streams, nstreams)
+    d_rects = torch.stack((d_image, d_x, d_y, d_w, d_h, d_dst), dim=1).contiguous()
+    scratch = _buffer(scratch, dataset_crop_scratch_bytes(nrects, max_w, max_h), torch.uint8, dev,
+                      "scratch smaller than dataset_crop_scratch_bytes(nrects, max_w, max_h)", floor=16)
+    d_result = _buffer(d_result, 3, torch.int64, dev)
+    _call("jpegr_dataset_crop_tensor_device", d_streams, nstreams, d_rects, nrects, d_flip, max_w, max_h,
+          code, _LAYOUTS[layout], scale3, bias3, d_out, out_cap, scratch, d_result, stream_arg(stream))
+    if not check:
+        return d_out, d_dst, None
+    n = _lib.batch_verdict(d_result, stream, JpegError, -1, "jpegr_dataset_crop_tensor_device: rectangle")
+    return d_out, d_dst, n
+
+
+def dataset_crop_resize_device(d_streams, nstreams, d_image, d_x, d_y, d_w, d_h, max_w, max_h, out_w, out_h,
+                               antialias=True, d_dst=None, d_out=None, out_cap=None, scratch=None,
+                               d_result=None, stream=None, check=True, dtype=None, layout="chw", scale=None,
+                               bias=None, d_flip=None):
+    """crop_resize_device over many streams in one call
+    (jpegr_dataset_crop_resize_device): d_streams, nstreams and d_image as for
+    dataset_crop_tensor_device; the scratch is
+    dataset_crop_resize_scratch_bytes(nrects, max_w, max_h, out_w, out_h)
+    bytes.  Everything else is crop_resize_device's."""
+    import torch
+    dtype, code = _tensor_dtype(dtype)
+    if layout not in _LAYOUTS:
+        raise ValueError('layout is "chw" or "hwc"')
+    if not (isinstance(out_w, int) and isinstance(out_h, int) and out_w > 0 and out_h > 0):
+        raise ValueError("out_w and out_h are positive ints")
+    scale3, bias3 = _float3(scale, "scale"), _float3(bias, "bias")
+    nrects = d_x.numel()
+    if d_flip is not None and (d_flip.dtype not in (torch.bool, torch.uint8) or d_flip.numel() != nrects):
+        raise ValueError("d_flip is a bool or uint8 tensor with one entry per crop")
+    if d_out is not None and d_out.dtype != dtype:
+        raise ValueError("d_out is not of the requested dtype")
+    per = 3 * out_w * out_h
+    dev = d_streams.device
+    if d_dst is None:
+        d_dst = torch.arange(nrects, dtype=torch.int64, device=d_x.device) * per
+    if out_cap is None:
+        out_cap = d_out.numel() if d_out is not None else nrects * per
+    d_out = _buffer(d_out, out_cap, dtype, dev, "d_out smaller than out_cap elements", floor=4)
+    if nrects == 0:
+        return d_out, d_dst, (0 if check else None)
+    _check_table(d_streams, nstreams)
+    d_rects = torch.stack((d_image, d_x, d_y, d_w, d_h, d_dst), dim=1).contiguous()
+    scratch = _buffer(scratch, dataset_crop_resize_scratch_bytes(nrects, max_w, max_h, out_w, out_h),
+                      torch.uint8, dev,
+                      "scratch smaller than dataset_crop_resize_scratch_bytes(nrects, max_w, max_h, out_w, out_h)",
+                      floor=16)
+    d_result = _buffer(d_result, 3, torch.int64, dev)
+    _call("jpegr_dataset_crop_resize_device", d_streams, nstreams, d_rects, nrects, d_flip, max_w, max_h,
+          out_w, out_h, 1 if antialias else 0, code, _LAYOUTS[layout], scale3, bias3, d_out, out_cap, scratch,
+          d_result, stream_arg(stream))
+    if not check:
+        return d_out, d_dst, None
+    n = _lib.batch_verdict(d_result, stream, JpegError, -1, "jpegr_dataset_crop_resize_device: rectangle")
+    return d_out, d_dst, n
+
+
 # -- thumbnails -----------------------------------------------------------------
 def thumb_device(d_stream, in_len, w, h, nimg, first=0, count=None, d_offsets=None, d_out=None,
                  d_dc=None, want_dc=False, scratch=None, d_result=None, stream=None):
@@ -822,6 +947,88 @@ class StreamReader:
     def transcode(self, tight):
         """The whole stream in the other (or the same) format: select of everything."""
         return self.select(tight=tight)
+
+
+class Dataset:
+    """Many streams read as one: StreamReaders of any sizes and either format,
+    in the order given, their images numbered through -- image g of the
+    dataset is image g - image0[s] of reader s.  Keeps the readers (and so their
+    streams and offsets) alive and builds the table of jpegr_stream_desc on
+    the device once.  image0: int64 array, each reader's first index; nimg: the
+    total; sizes: int64 array [nimg, 2], every image's (w, h), on the host,
+    for a sampler to draw rectangles from; max_w, max_h: the largest stream's
+    width and height, the default bound on a rectangle."""
+
+    def __init__(self, readers):
+        import torch
+        self.readers = list(readers)
+        if not self.readers:
+            raise ValueError("no readers")
+        counts = np.array([rd.nimg for rd in self.readers], np.int64)
+        self.image0 = np.cumsum(counts) - counts
+        self.nimg = int(counts.sum())
+        self.sizes = np.repeat(np.array([(rd.w, rd.h) for rd in self.readers], np.int64), counts, axis=0)
+        self.max_w = max(rd.w for rd in self.readers)
+        self.max_h = max(rd.h for rd in self.readers)
+        self.table = stream_table((rd.d_stream.data_ptr(), rd.length, rd.d_offsets.data_ptr(), i0, rd.w, rd.h,
+                                   rd.nimg) for rd, i0 in zip(self.readers, self.image0))
+        self.device = self.readers[0].d_stream.device
+        self.d_table = torch.from_numpy(self.table.view(np.int64)).to(self.device)
+
+    def crops_tensor(self, d_image, d_x, d_y, d_w, d_h, max_w=None, max_h=None, **kw):
+        """dataset_crop_tensor_device on these streams: (d_out, d_dst, delivered)."""
+        return dataset_crop_tensor_device(self.d_table, len(self.readers), d_image, d_x, d_y, d_w, d_h,
+                                          self.max_w if max_w is None else max_w,
+                                          self.max_h if max_h is None else max_h, **kw)
+
+    def crops_resized(self, d_image, d_x, d_y, d_w, d_h, out_w, out_h, max_w=None, max_h=None, **kw):
+        """dataset_crop_resize_device on these streams: (d_out, d_dst, delivered)."""
+        return dataset_crop_resize_device(self.d_table, len(self.readers), d_image, d_x, d_y, d_w, d_h,
+                                          self.max_w if max_w is None else max_w,
+                                          self.max_h if max_h is None else max_h, out_w, out_h, **kw)
+
+    def crop_batch(self, d_image, d_x, d_y, w, h, dtype=None, layout="chw", mean=None, std=None,
+                   d_flip=None):
+        """StreamReader.crop_batch with a dataset-wide d_image: n crops of
+        w x h pixels, each from its own stream, as one [n, 3, h, w] or
+        [n, h, w, 3] tensor, in one call."""
+        import torch
+        dtype, _ = _tensor_dtype(dtype)
+        if layout not in _LAYOUTS:
+            raise ValueError('layout is "chw" or "hwc"')
+        scale, bias = normalisation(mean, std)
+        n = d_x.numel()
+        shape = (n, 3, h, w) if layout == "chw" else (n, h, w, 3)
+        d_out = torch.empty(n * 3 * w * h, dtype=dtype, device=self.device)
+        if n and w and h:
+            d_dst = torch.arange(n, dtype=torch.int64, device=self.device) * (3 * w * h)
+            self.crops_tensor(d_image, d_x, d_y, torch.full_like(d_x, w), torch.full_like(d_x, h), w, h,
+                              d_dst=d_dst, d_out=d_out, out_cap=d_out.numel(), dtype=dtype,
+                              layout=layout, scale=scale, bias=bias, d_flip=d_flip)
+        return d_out.view(shape)
+
+    def resized_crop_batch(self, d_image, d_x, d_y, d_w, d_h, out_w, out_h, antialias=True, dtype=None,
+                           layout="chw", mean=None, std=None, d_flip=None, max_w=None, max_h=None):
+        """StreamReader.resized_crop_batch with a dataset-wide d_image:
+        RandomResizedCrop's batch from images of many sizes in one call.
+        max_w, max_h: bounds on d_w and d_h, by default the largest stream's
+        size (no read-back; the scratch and the decode's idle items grow with
+        them, so pass the sampler's own bounds where it has them)."""
+        import torch
+        dtype, _ = _tensor_dtype(dtype)
+        if layout not in _LAYOUTS:
+            raise ValueError('layout is "chw" or "hwc"')
+        if not (isinstance(out_w, int) and isinstance(out_h, int) and out_w > 0 and out_h > 0):
+            raise ValueError("out_w and out_h are positive ints")
+        scale, bias = normalisation(mean, std)
+        n = d_x.numel()
+        shape = (n, 3, out_h, out_w) if layout == "chw" else (n, out_h, out_w, 3)
+        d_out = torch.empty(n * 3 * out_w * out_h, dtype=dtype, device=self.device)
+        if n:
+            self.crops_resized(d_image, d_x, d_y, d_w, d_h, out_w, out_h, max_w=max_w, max_h=max_h,
+                               antialias=antialias, d_out=d_out, out_cap=d_out.numel(), dtype=dtype,
+                               layout=layout, scale=scale, bias=bias, d_flip=d_flip)
+        return d_out.view(shape)
 
 
 def stream_encode_scratch_bytes(ntiles, cap):

@@ -8,7 +8,7 @@ launches.
                                     [--decode | --tight [--against LIB] | --direct [--against LIB]
                                      | --crop [--against LIB] | --thumb [--against LIB]
                                      | --select [--against LIB] | --tensor [--against LIB]
-                                     | --resize]
+                                     | --resize | --dataset]
 
 Images: bench.py's 3840x2160 random image (synth.rand_rgba_device, seed 1)
 and a 3840x2160 smooth one (tests/test_gpu_entropy.py's generator).  Prints
@@ -121,7 +121,18 @@ batch, the flip, and to(bfloat16); and (b) crop_tensor_device of the same
 rectangles alone, with no resampling, as the floor.  The fused float32 output
 is compared with the chain's before anything is timed: they are not bit-equal
 by design (include/jpegr.h), so the largest |difference| is reported.  With
---once N: N fused calls of each dtype per stream and nothing else."""
+--once N: N fused calls of each dtype per stream and nothing else.
+
+--dataset: crops from many streams in one call
+(jpegr_dataset_crop_resize_device), for DESIGN 4.18: 256 streams of different
+sizes (320 .. 546 by 240 .. 420, two random images each, JPR1 and JPT1
+alternating); 256 RandomResizedCrop rectangles to 224 x 224 float32 CHW, every
+second one mirrored, rectangle r from stream r % S, for S = 1, 16 and 256.  One
+dataset call beside the S jpegr_crop_resize_device calls that write the same
+tensor (each with its own rectangles, local image indices and the same dst),
+both as bare C calls on prepared rectangles, outputs compared bitwise first,
+then alternated over --rounds rounds, event-timed.  With --once N: N dataset
+calls per S and nothing else."""
 import argparse
 import json
 import os
@@ -987,6 +998,92 @@ def resize_side(args, torch, jpeg, synth, dev):
             del d_stream
 
 
+def dataset_sizes(s):
+    """Stream s's (w, h): 320 .. 546 by 240 .. 420, no two neighbours alike."""
+    return 320 + 8 * (s % 29) + s % 3, 240 + 8 * ((7 * s) % 23) + s % 5
+
+
+def dataset_side(args, torch, jpeg, synth, dev):
+    """One jpegr_dataset_crop_resize_device call beside the S
+    jpegr_crop_resize_device calls that write the same tensor."""
+    from lz4jpeg import _lib
+    nimg = 2
+    scale, bias = jpeg.normalisation(IMAGENET_MEAN, IMAGENET_STD)
+    scale3, bias3 = jpeg._float3(scale, "scale"), jpeg._float3(bias, "bias")
+    per = 3 * CROP * CROP
+    capo = NCROPS * per
+    d_flip = torch.from_numpy((np.arange(NCROPS) % 2).astype(np.uint8)).to(dev)
+    d_out = [torch.empty(capo, dtype=torch.float32, device=dev) for _ in range(2)]
+    d_res = torch.empty(3, dtype=torch.int64, device=dev)
+    d_sres = torch.empty(256, 3, dtype=torch.int64, device=dev)
+    stream = jpeg.stream_arg(None)
+    readers = []
+    for s in range(256):
+        w, h = dataset_sizes(s)
+        d_img = torch.empty(nimg * w * h * 4, dtype=torch.uint8, device=dev)
+        synth.rand_rgba_device(d_img, 0, nimg * w * h, seed=1 + s)
+        readers.append(jpeg.StreamReader(jpeg.compress_device(d_img, w, h, nimg, tight=bool(s & 1))))
+    for S in (1, 16, 256):
+        rng = np.random.default_rng(7)
+        ds = jpeg.Dataset(readers[:S])
+        rects = []                                          # rectangle r from stream r % S
+        for r in range(NCROPS):
+            rd = readers[r % S]
+            im, x, y, cw, ch = random_resized_rects(rng, 1, rd.w, rd.h, nimg)[0]
+            rects.append((int(ds.image0[r % S]) + im, x, y, cw, ch, r * per))
+        mw, mh = max(r[3] for r in rects), max(r[4] for r in rects)
+        d_rects = torch.from_numpy(np.asarray(rects, np.int64)).to(dev)
+        scr = torch.empty(jpeg.dataset_crop_resize_scratch_bytes(NCROPS, mw, mh, CROP, CROP), dtype=torch.uint8,
+                          device=dev)
+        singles = []                                        # per stream: its rectangles with local image indices
+        for s in range(S):
+            rows = list(range(s, NCROPS, S))
+            local = [(rects[r][0] - int(ds.image0[s]),) + rects[r][1:] for r in rows]
+            singles.append((readers[s], torch.from_numpy(np.asarray(local, np.int64)).to(dev), len(rows),
+                            d_flip[rows].contiguous(), min(mw, readers[s].w), min(mh, readers[s].h)))
+
+        def dataset():
+            checked(_lib.call("jpegr_dataset_crop_resize_device", ds.d_table, S, d_rects, NCROPS, d_flip, mw, mh,
+                              CROP, CROP, 1, 1, 0, scale3, bias3, d_out[0], capo, scr, d_res, stream))
+
+        def per_stream():
+            for s, (rd, d_loc, n, d_fl, smw, smh) in enumerate(singles):
+                checked(_lib.call("jpegr_crop_resize_device", rd.d_stream, rd.length, rd.w, rd.h, rd.nimg,
+                                  rd.d_offsets, d_loc, n, d_fl, smw, smh, CROP, CROP, 1, 1, 0, scale3, bias3,
+                                  d_out[1], capo, scr, d_sres[s], stream))
+
+        calls = [("dataset", dataset), ("per_stream", per_stream)]
+        if args.once:
+            for _ in range(args.once):
+                dataset()
+            torch.cuda.synchronize()
+            continue
+        d_out[0].fill_(-1.0)
+        d_out[1].fill_(-2.0)
+        dataset()
+        per_stream()
+        ok = d_res.cpu().tolist() == [NCROPS, -1, 0]
+        ok = ok and d_sres[:S].cpu().tolist() == [[len(range(s, NCROPS, S)), -1, 0] for s in range(S)]
+        steps = max(4, args.steps // max(1, S // 4))
+        res = {"streams": S, "sizes": "320..546 x 240..420, JPR1 and JPT1 alternating, 2 images each",
+               "crops": f"{NCROPS} RandomResizedCrop rectangles to {CROP}x{CROP} float32 CHW, every second one "
+                        "mirrored", "max_w": mw, "max_h": mh, "verdicts_ok": ok,
+               "outputs_equal": bool(torch.equal(d_out[0].view(torch.int32), d_out[1].view(torch.int32))),
+               "steps": steps, "rounds": args.rounds, "scratch_bytes": scr.numel()}
+        ms = {k: [] for k, _ in calls}
+        for r in range(args.rounds):                        # alternated; the order turns with the round
+            for key, fn in calls[r % 2:] + calls[:r % 2]:
+                settle(fn, torch.cuda.synchronize, chunk=1)
+                ms[key].append(timed(fn, steps, torch))
+        for key, _ in calls:
+            res[key + "_ms"] = spread(ms[key])
+        res["dataset_over_per_stream"] = {
+            "min": round(min(a / b for a, b in zip(ms["dataset"], ms["per_stream"])), 4),
+            "median": round(res["dataset_ms"]["median"] / res["per_stream_ms"]["median"], 4),
+            "max": round(max(a / b for a, b in zip(ms["dataset"], ms["per_stream"])), 4)}
+        print(json.dumps(res), flush=True)
+
+
 def thumb_side(args, torch, jpeg, synth, dev, other):
     """Thumbnails straight from the stream beside decode-everything-and-pool."""
     import ctypes
@@ -1270,6 +1367,7 @@ def main():
     ap.add_argument("--select", action="store_true")
     ap.add_argument("--tensor", action="store_true")
     ap.add_argument("--resize", action="store_true")
+    ap.add_argument("--dataset", action="store_true")
     ap.add_argument("--against", default=None,
                     help="with --tight, --direct, --crop, --select or --tensor: a second liblz4jpeg.so to "
                          "alternate with; with --thumb: that, or a second build of jpegr_thumb.hip "
@@ -1280,12 +1378,14 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("jpeg_pack_bench: needs a GPU (there is no CPU path to time)")
     dev = torch.device("cuda:0")
-    if args.crop or args.thumb or args.select or args.tensor or args.resize:
+    if args.crop or args.thumb or args.select or args.tensor or args.resize or args.dataset:
         if not args.once:                   # clock pre-warm (bench.py run_lz4)
             d_warm = torch.zeros(256 << 20, dtype=torch.uint8, device=dev)
             settle(lambda: d_warm.add_(1), torch.cuda.synchronize, ms=100.0, chunk=16)
             del d_warm
-        if args.resize:
+        if args.dataset:
+            dataset_side(args, torch, jpeg, synth, dev)
+        elif args.resize:
             resize_side(args, torch, jpeg, synth, dev)
         elif args.tensor:
             tensor_side(args, torch, jpeg, synth, dev, second_build(args.against) if args.against else None)

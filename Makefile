@@ -4,6 +4,7 @@
 #   lz4-jpeg_amd/lz4jpeg/liblz4jpeg.so   product C-ABI library (HIP kernels)
 #   lz4-jpeg_amd/bin/LZ4_seq, JPEG_seq    drop-in executables (file contract),
 #                                         also as LZ4_seq.exe / JPEG_seq.exe
+#   lz4-jpeg_amd/bin/LZ4_frame            file -> standard .lz4 frame on the GPU, -d back on the host (also LZ4_frame.exe)
 #   lz4-jpeg_amd/bin/JPEG_dec             coefficients.jpr -> PNG (also JPEG_dec.exe)
 #   lz4-jpeg_amd/bin/JPEG_sel             images or tile windows of a .jpr -> a new .jpr (also JPEG_sel.exe)
 #   oracle/liboracle.so (+ oracle/_ref)   test-only CPU checker
@@ -38,6 +39,7 @@ HDRS    := include/lz4r.h include/jpegr.h include/lz4jpeg_compat.h include/lz4jp
            $(CSRC)/jpeg_tables.h $(CSRC)/jpeg_tables_dev.h \
            $(CSRC)/wave64.h $(CSRC)/lz4r_prof.h $(CSRC)/lz4r_layout.h $(CSRC)/lz4r_tile_lds.h \
            $(CSRC)/lz4r_tiles.h $(CSRC)/lz4r_matches.h $(CSRC)/lz4r_scan.h $(CSRC)/lz4r_emit.h \
+           $(CSRC)/lz4r_frame.h $(HOST)/lz4f_xxh32.h \
            $(CSRC)/lz4r_dec_layout.h $(CSRC)/lz4r_dec_parse.h $(CSRC)/lz4r_dec_blocks.h \
            $(CSRC)/lz4r_dec_bare.h $(CSRC)/lz4r_dec_read.h $(CSRC)/jpegr_pack_common.h \
            $(CSRC)/jpegr_entropy_common.h $(CSRC)/jpegr_decode_common.h $(CSRC)/jpegr_crop.h \
@@ -47,7 +49,7 @@ OBJS    := $(B)/lz4r.o $(B)/lz4r_gpudec.o $(B)/lz4r_read.o $(B)/jpegr.o $(B)/jpe
            $(B)/jpegr_entropy.o $(B)/jpegr_pack.o $(B)/jpegr_stream.o $(B)/jpegr_stream_enc.o \
            $(B)/jpegr_thumb.o $(B)/jpegr_select.o $(B)/jpegr_resize.o \
            $(B)/synth.o $(B)/synth_dev.o \
-           $(B)/lz4r_decode.o $(B)/compat.o $(B)/compat_lz4.o
+           $(B)/lz4r_decode.o $(B)/lz4f_decode.o $(B)/compat.o $(B)/compat_lz4.o
 
 all: lib bin oracle tools chunk12
 
@@ -55,7 +57,8 @@ lib: $(LIB)
 
 bin: $(BIN)/LZ4_seq $(BIN)/JPEG_seq $(BIN)/LZ4_seq.exe $(BIN)/JPEG_seq.exe \
      $(BIN)/LZ4_par $(BIN)/JPEG_par $(BIN)/LZ4_par.exe $(BIN)/JPEG_par.exe \
-     $(BIN)/JPEG_dec $(BIN)/JPEG_dec.exe $(BIN)/JPEG_sel $(BIN)/JPEG_sel.exe
+     $(BIN)/JPEG_dec $(BIN)/JPEG_dec.exe $(BIN)/JPEG_sel $(BIN)/JPEG_sel.exe \
+     $(BIN)/LZ4_frame $(BIN)/LZ4_frame.exe
 
 $(CSRC)/jpeg_tables.h: $(CSRC)/gen_jpeg_tables.py
 	python3 $< > $@
@@ -97,6 +100,10 @@ $(CHUNK12_LIB): $(CSRC)/lz4r.hip $(HDRS)
 # how JPEG_dec and JPEG_sel open a .jpr file: the executables' alone, not the library's
 JPR_FILE_OBJS := $(B)/jpr_file.o $(B)/read_file.o
 $(BIN)/LZ4_seq: $(B)/lz4_seq.o $(OBJS)
+	@mkdir -p $(BIN)
+	$(HIPCC) --offload-arch=$(ARCH) -o $@ $^
+
+$(BIN)/LZ4_frame: $(B)/lz4_frame.o $(B)/read_file.o $(OBJS)
 	@mkdir -p $(BIN)
 	$(HIPCC) --offload-arch=$(ARCH) -o $@ $^
 
@@ -154,6 +161,15 @@ build/sanitize_main: $(SAN_SRC) $(SAN_CXX_OBJ) include/lz4r.h include/lz4jpeg_sy
 	@mkdir -p build
 	$(CC) $(SAN_FLAGS) -std=gnu11 -o $@ $(SAN_SRC) $(SAN_CXX_OBJ) -lz -lm -lpthread
 
+# ASan + UBSan build of the standard-frame decoder alone (host/lz4f_decode.c),
+# driven by tests/sanitize/frame_main.c; tests/test_sanitize_frame.py
+sanitize-frame: build/sanitize_frame
+	./build/sanitize_frame
+
+build/sanitize_frame: tests/sanitize/frame_main.c $(HOST)/lz4f_decode.c $(HOST)/lz4f_xxh32.h include/lz4r.h
+	@mkdir -p build
+	$(CC) $(SAN_FLAGS) -std=gnu11 -Wall -o $@ tests/sanitize/frame_main.c $(HOST)/lz4f_decode.c
+
 # micro-benchmarks: SIMD issue rates (tools/issue.sh) and LDS access costs
 tools: tools/ab/valu_rate tools/ab/lds_rate
 
@@ -169,7 +185,7 @@ clean:
 	rm -rf $(B) $(BIN) $(LIB) build
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib bin oracle tools chunk12 thumb-alt sanitize clean
+.PHONY: all lib bin oracle tools chunk12 thumb-alt sanitize sanitize-frame clean
 
 # `make -s print-HIPFLAGS`: a variable's value (tests/test_isa.py builds with the product flags)
 print-%:

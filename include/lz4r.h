@@ -250,6 +250,59 @@ int lz4r_stream_index_device(const void *d_in, size_t in_len, void *d_block_offs
 int lz4r_compress(const uint8_t *in, size_t n, uint8_t *out, size_t cap,
                   size_t *out_len);
 
+/* ---- standard LZ4 frames -------------------------------------------------
+ * The same parse (the reference's greedy longest-match parse of every 300-byte
+ * block) written as a standard LZ4 frame, which `lz4 -d`, liblz4 and every
+ * other LZ4 frame reader decode: LZ4 Frame Format 1.6.x, magic 04 22 4D 18,
+ * FLG 0x68 (version 01, independent blocks, content size present, no
+ * checksums, no dictionary ID), BD 0x40 (64 KiB block maximum), u64 content
+ * size = n, header checksum; then one data block per 64 source blocks (19,200
+ * input bytes; the last one what is left), each a u32 size and that many
+ * bytes, always stored compressed (the high bit is never set, so the bytes are
+ * deterministic), then the EndMark 00 00 00 00.  A data block's sequences are
+ * its source blocks' matches under the block format's end rules: a match of
+ * fewer than 4 stored bytes or one that starts in the data block's last 11
+ * bytes becomes literals, one that reaches into its last 5 bytes is cut, and
+ * literal runs merge across source blocks (csrc/lz4r_frame.h).
+ *
+ * Worst-case frame size of n input bytes: 19 + n + 100 per data block (header
+ * 15, EndMark 4; per data block of N <= 19,200 bytes the u32 size, N / 255
+ * literal-length bytes, the last token and one more extension byte: <= 81). */
+size_t lz4r_frame_bound(size_t n);
+
+/* lz4r_compress_async's and lz4r_compress_device's contracts, for a standard
+ * frame: the length word holds the need when it exceeds cap (nothing at or
+ * past cap is written), bit 63 is the corrupt-index verdict, n < 300 is
+ * LZ4R_ERR_TOO_SMALL, d_in and d_out take any alignment, the async form
+ * enqueues only (no host read-back: it can be captured into a graph).
+ * A frame call leaves no per-block arrays: after it lz4r_copy_block_sizes,
+ * lz4r_copy_block_offsets and lz4r_block_offsets_device, which describe native
+ * streams, return LZ4R_ERR_ARG (not a stale array) until the next native call
+ * on the context. */
+int lz4r_compress_frame_async(lz4r_ctx *ctx, const void *d_in, size_t n,
+                              void *d_out, size_t cap, void *d_out_len,
+                              void *stream);
+int lz4r_compress_frame_device(lz4r_ctx *ctx, const void *d_in, size_t n,
+                               void *d_out, size_t cap, size_t *out_len,
+                               void *stream);
+
+/* Host-buffer form of lz4r_compress_frame_device (copies in and out). */
+int lz4r_compress_frame(const uint8_t *in, size_t n, uint8_t *out, size_t cap,
+                        size_t *out_len);
+
+/* Decode standard LZ4 frames on the host (host/lz4f_decode.c): exact and
+ * bounds-checked, for any conforming frame, not only this library's --
+ * linked or independent blocks, stored blocks, content size present or
+ * absent; the header checksum is verified, block and content checksums when
+ * their flags are set.  Concatenated frames decode to the concatenation (one
+ * frame per GPU shard is a valid file).  LZ4R_ERR_CORRUPT on anything
+ * malformed or unsupported: an empty or truncated input, a dictionary ID, a
+ * reserved bit, a skippable or legacy magic, a wrong checksum, a content size
+ * that does not match.  LZ4R_ERR_CAPACITY sets *out_len to the length needed
+ * so far.  Never reads outside in[0, in_len) or writes outside out[0, cap). */
+int lz4r_frame_decompress(const uint8_t *in, size_t in_len, uint8_t *out,
+                          size_t cap, size_t *out_len);
+
 /* Synchronise `stream` and report whether the last compress call on ctx met
  * a corrupt bucket head in lz4_tiles' LDS index (a head that is neither empty
  * nor an earlier position of the block: never on a sound LDS; the walk ends

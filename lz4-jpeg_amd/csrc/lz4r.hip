@@ -18,6 +18,8 @@
 //   lz4r_scan.h      lz4_scan_reduce16, lz4_scan_partials_frame: exclusive scan
 //                    of the byte counts
 //   lz4r_emit.h      lz4_emit: 32 blocks per workgroup, records -> stream bytes
+//   lz4r_frame.h     lz4f_sizes, lz4f_scan, lz4f_emit: the same records as a
+//                    standard LZ4 frame (the lz4r_compress_frame_* calls)
 //   wave64.h         the wave-level helpers all of them use
 //   lz4r_prof.h      PROF_MARK: nothing in the product, cycle counters or
 //                    assembly markers in the tools builds
@@ -46,6 +48,8 @@
 #include "lz4r_matches.h"
 #include "lz4r_scan.h"
 #include "lz4r_emit.h"
+#include "lz4r_frame.h"
+#include "../host/lz4f_xxh32.h"
 
 // Launch chunking: lz4_tiles was a 64-lane workgroup per block (now per run
 // of kTileRun blocks; the chunk size stayed), and a HIP
@@ -81,6 +85,7 @@ struct lz4r_ctx {
   uint32_t *status = nullptr;  // (len + 1) nonzero once a block saw a corrupt bucket head
   uint64_t *verdict = nullptr; // (len + 2) the last call's corrupt-index verdict (0 / 1)
   size_t last_nb = 0;
+  bool last_frame = false;     // the last call wrote a standard frame: no per-block arrays
   bool checkable = false;      // a call has launched (lz4r_check has a verdict to read)
   // timing: per timed call since lz4r_set_timing(1), the call's start/end
   // events and lz4_tiles' start/end in every chunk (a ring of kTimedCalls
@@ -187,10 +192,21 @@ int timed_ms(const lz4r_ctx::timed_set &t, float *ms_call, float *ms_match) {
   return LZ4R_OK;
 }
 
+// The header of a standard frame of n content bytes (lz4r_frame.h): magic,
+// FLG 0x68 (version 01, independent blocks, content size), BD 0x40 (64 KiB
+// block maximum), the size, HC = the second byte of xxh32(FLG .. size).
+void frame_header(size_t n, uint8_t h[kFrameHdr]) {
+  const uint8_t fixed[6] = {0x04, 0x22, 0x4D, 0x18, 0x68, 0x40};
+  for (int i = 0; i < 6; ++i) h[i] = fixed[i];
+  for (int i = 0; i < 8; ++i) h[6 + i] = (uint8_t)((uint64_t)n >> (8 * i));
+  h[14] = (uint8_t)(lz4f_xxh32(h + 4, 10, 0) >> 8);
+}
+
 // hdr = 1: a framed stream (frame byte first).  hdr = 0: a segment of whole
-// blocks for one shard of a multi-GPU job (no frame byte).
+// blocks for one shard of a multi-GPU job (no frame byte).  frame_out: a
+// standard LZ4 frame of the same parse instead (hdr = 1).
 int run(lz4r_ctx *c, const void *d_in, size_t n, void *d_out, size_t cap,
-        void *d_len, int hdr, void *stream) {
+        void *d_len, int hdr, void *stream, bool frame_out = false) {
   if (!c || !d_in || !d_out || !d_len) return LZ4R_ERR_ARG;
   if (hdr && n < (size_t)kBlk) return LZ4R_ERR_TOO_SMALL;
   if (n == 0 || n > kMaxInput) return LZ4R_ERR_ARG;
@@ -208,6 +224,12 @@ int run(lz4r_ctx *c, const void *d_in, size_t n, void *d_out, size_t cap,
   // lz4_tiles start .. the last lz4_emit stop.
   auto ev = [&](hipEvent_t e) { return timed ? e : nullptr; };
   const uint8_t *in = static_cast<const uint8_t *>(d_in);
+  uint64_t fh0 = 0, fh1 = 0;           // the frame header, as lz4f_scan takes it
+  if (frame_out) {
+    uint8_t h[kFrameHdr];
+    frame_header(n, h);
+    for (int i = 0; i < kFrameHdr; ++i) (i < 8 ? fh0 : fh1) |= (uint64_t)h[i] << (8 * (i & 7));
+  }
   // the block scratch: cap_slots heads of kHead bytes, then the overflow slots
   uint8_t *const ovfs = c->slots + c->cap_slots * (size_t)kHead;
   for (size_t k = 0; k < nchunks; ++k) {
@@ -227,6 +249,25 @@ int run(lz4r_ctx *c, const void *d_in, size_t n, void *d_out, size_t cap,
     const auto tiles = ((uintptr_t)in & 3) == 0 ? lz4_tiles<true> : lz4_tiles<false>;
     hipExtLaunchKernelGGL(tiles, dim3(8 * runs), dim3(64), 0, s, t0, t1, 0u, in + b0 * kBlk,
                           (uint32_t)nbc, per, last_n, c->slots, ovfs, c->bsizes + b0, c->status);
+    if (frame_out) {
+      // the records as a standard frame (lz4r_frame.h): a data block per scan
+      // group; its stream offset takes the place of the group's first block's
+      // in boff (a frame call leaves no per-block arrays)
+      const size_t g0 = b0 / kGT, ng = (nbc + kGT - 1) / kGT;
+      const bool last = k + 1 == nchunks;
+      hipLaunchKernelGGL(lz4f_sizes, dim3((unsigned)ng), dim3(64 * kFW), 0, s,
+                         (const uint8_t *)c->slots, (const uint8_t *)ovfs, (uint32_t)nbc, last_n,
+                         c->boff + g0);
+      hipLaunchKernelGGL(lz4f_scan, dim3(1), dim3(1024), 0, s, c->boff + g0, ng, k == 0 ? 1 : 0,
+                         last ? 1 : 0, c->status, static_cast<uint64_t *>(d_len), c->verdict,
+                         static_cast<uint8_t *>(d_out), (uint64_t)cap, fh0, fh1);
+      hipExtLaunchKernelGGL(lz4f_emit, dim3((unsigned)ng), dim3(64 * kFW), 0, s, nullptr,
+                            last ? ev(ts ? ts->c : nullptr) : nullptr, 0u, in + b0 * kBlk,
+                            (const uint8_t *)c->slots, (const uint8_t *)ovfs, (uint32_t)nbc, last_n,
+                            (const uint64_t *)(c->boff + g0), static_cast<uint8_t *>(d_out),
+                            (uint64_t)cap);
+      continue;
+    }
     // the chunk's own groups and partials (a chunk starts on a partial)
     const size_t p0 = b0 / kPart, np = (nbc + kPart - 1) / kPart;
     const size_t g0 = b0 / kGT, ng = (nbc + kGT - 1) / kGT;
@@ -250,7 +291,8 @@ int run(lz4r_ctx *c, const void *d_in, size_t n, void *d_out, size_t cap,
                           c->boff + b0);
   }
   if (timed) ++c->timed_calls;
-  c->last_nb = nb;
+  c->last_nb = frame_out ? 0 : nb;
+  c->last_frame = frame_out;
   c->checkable = true;
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess && getenv("LZ4R_DEBUG"))
@@ -318,6 +360,7 @@ int lz4r_compress_segment_async(lz4r_ctx *c, const void *d_in, size_t n, void *d
   if (!final_shard && n % kBlk != 0) return LZ4R_ERR_ARG;
   if (n == 0) {                      // an empty shard (more ranks than blocks)
     c->last_nb = 0;
+    c->last_frame = false;
     c->checkable = false;     // nothing launched: lz4r_check reports OK
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (c->timing) {          // a timed call of no launches
@@ -333,10 +376,11 @@ int lz4r_compress_segment_async(lz4r_ctx *c, const void *d_in, size_t n, void *d
   return run(c, d_in, n, d_out, cap, d_len, 0, stream);
 }
 
-int lz4r_compress_device(lz4r_ctx *c, const void *d_in, size_t n, void *d_out, size_t cap,
-                         size_t *out_len, void *stream) {
+// run() into the context's own length word, then the length read back
+static int run_device(lz4r_ctx *c, const void *d_in, size_t n, void *d_out, size_t cap,
+                      size_t *out_len, void *stream, bool frame_out) {
   if (!c || !out_len) return LZ4R_ERR_ARG;
-  int rc = run(c, d_in, n, d_out, cap, c->len, 1, stream);
+  int rc = run(c, d_in, n, d_out, cap, c->len, 1, stream, frame_out);
   if (rc != LZ4R_OK) return rc;
   uint64_t got = 0;                    // the length, with the corrupt flag: one read-back
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -349,6 +393,29 @@ int lz4r_compress_device(lz4r_ctx *c, const void *d_in, size_t n, void *d_out, s
   *out_len = (size_t)(got & ~kLenCorrupt);
   if (got & kLenCorrupt) return LZ4R_ERR_CORRUPT;   // a corrupt bucket head
   return *out_len > cap ? LZ4R_ERR_CAPACITY : LZ4R_OK;
+}
+
+int lz4r_compress_device(lz4r_ctx *c, const void *d_in, size_t n, void *d_out, size_t cap,
+                         size_t *out_len, void *stream) {
+  return run_device(c, d_in, n, d_out, cap, out_len, stream, false);
+}
+
+// Per data block of N bytes: the u32 size, and a sequence expands the bytes
+// it covers by at most L / 255 (a kept match adds 3 + its extensions and saves
+// >= 4), the last run by its token and one more extension byte:
+// 4 + N + N / 255 + 2 <= N + 81 for N <= 19,200.  Header 15, EndMark 4.
+size_t lz4r_frame_bound(size_t n) {
+  return 19 + n + 100 * ((n + (size_t)kFrameIn - 1) / (size_t)kFrameIn);
+}
+
+int lz4r_compress_frame_async(lz4r_ctx *c, const void *d_in, size_t n, void *d_out, size_t cap,
+                              void *d_len, void *stream) {
+  return run(c, d_in, n, d_out, cap, d_len, 1, stream, true);
+}
+
+int lz4r_compress_frame_device(lz4r_ctx *c, const void *d_in, size_t n, void *d_out, size_t cap,
+                               size_t *out_len, void *stream) {
+  return run_device(c, d_in, n, d_out, cap, out_len, stream, true);
 }
 
 int lz4r_block_matches_device(const void *d_in, size_t n, void *d_matches, void *stream) {
@@ -381,30 +448,32 @@ int lz4r_window_matches_device(const void *d_in, size_t n, void *d_matches, void
 }
 
 int lz4r_copy_block_sizes(const lz4r_ctx *c, void *dst, size_t count, void *stream) {
-  if (!c) return LZ4R_ERR_ARG;
+  if (!c || c->last_frame) return LZ4R_ERR_ARG;
   return copy_per_block(c, c->bsizes, sizeof(uint16_t), dst, count, stream);
 }
 
 int lz4r_copy_block_offsets(const lz4r_ctx *c, void *dst, size_t count, void *stream) {
-  if (!c) return LZ4R_ERR_ARG;
+  if (!c || c->last_frame) return LZ4R_ERR_ARG;
   return copy_per_block(c, c->boff, sizeof(uint64_t), dst, count, stream);
 }
 
 int lz4r_block_offsets_device(const lz4r_ctx *c, const void **d_offsets, size_t *count) {
-  if (!c || !d_offsets || !count) return LZ4R_ERR_ARG;
+  if (!c || !d_offsets || !count || c->last_frame) return LZ4R_ERR_ARG;
   *d_offsets = c->boff;
   *count = c->last_nb;
   return LZ4R_OK;
 }
 
-int lz4r_compress(const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *out_len) {
+// the host-buffer forms: copy in, compress (natively or as a frame), copy out
+static int compress_host(const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *out_len,
+                         bool frame_out) {
   if (!in || !out || !out_len) return LZ4R_ERR_ARG;
   if (n < (size_t)kBlk) return LZ4R_ERR_TOO_SMALL;
   lz4r_ctx *c = nullptr;
   int rc = lz4r_ctx_create(&c);
   if (rc != LZ4R_OK) return rc;
   void *din = nullptr, *dout = nullptr;
-  const size_t dcap = lz4r_compress_bound(n);
+  const size_t dcap = frame_out ? lz4r_frame_bound(n) : lz4r_compress_bound(n);
   if (hipMalloc(&din, n + 16) != hipSuccess || hipMalloc(&dout, dcap) != hipSuccess) {
     (void)hipFree(din);
     lz4r_ctx_destroy(c);
@@ -412,7 +481,7 @@ int lz4r_compress(const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t 
   }
   if (hipMemcpy(din, in, n, hipMemcpyHostToDevice) != hipSuccess) rc = LZ4R_ERR_HIP;
   size_t got = 0;
-  if (rc == LZ4R_OK) rc = lz4r_compress_device(c, din, n, dout, dcap, &got, nullptr);
+  if (rc == LZ4R_OK) rc = run_device(c, din, n, dout, dcap, &got, nullptr, frame_out);
   if (rc == LZ4R_OK) {
     *out_len = got;
     if (got > cap) rc = LZ4R_ERR_CAPACITY;
@@ -422,6 +491,14 @@ int lz4r_compress(const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t 
   (void)hipFree(dout);
   lz4r_ctx_destroy(c);
   return rc;
+}
+
+int lz4r_compress(const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *out_len) {
+  return compress_host(in, n, out, cap, out_len, false);
+}
+
+int lz4r_compress_frame(const uint8_t *in, size_t n, uint8_t *out, size_t cap, size_t *out_len) {
+  return compress_host(in, n, out, cap, out_len, true);
 }
 
 int lz4r_check(lz4r_ctx *c, void *stream) {

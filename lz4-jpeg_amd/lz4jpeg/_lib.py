@@ -32,6 +32,12 @@ SIGNATURES = [
     ("lz4r_window_matches_device", _i, [_vp, _c_size, _vp, _vp]),
     ("lz4r_compress", _i, [_vp, _c_size, _vp, _c_size, ctypes.POINTER(_c_size)]),
     ("lz4r_decompress", _i, [_vp, _c_size, _vp, _c_size, ctypes.POINTER(_c_size)]),
+    ("lz4r_frame_bound", _c_size, [_c_size]),
+    ("lz4r_compress_frame_async", _i, [_vp, _vp, _c_size, _vp, _c_size, _vp, _vp]),
+    ("lz4r_compress_frame_device", _i, [_vp, _vp, _c_size, _vp, _c_size, ctypes.POINTER(_c_size),
+                                        _vp]),
+    ("lz4r_compress_frame", _i, [_vp, _c_size, _vp, _c_size, ctypes.POINTER(_c_size)]),
+    ("lz4r_frame_decompress", _i, [_vp, _c_size, _vp, _c_size, ctypes.POINTER(_c_size)]),
     ("lz4r_decompress_device", _i, [_vp, _c_size, _vp, _c_size, _vp, _c_size, _vp, _vp]),
     ("lz4r_decompress_stream_device", _i, [_vp, _c_size, _vp, _c_size, ctypes.POINTER(_c_size),
                                            _vp]),

@@ -42,6 +42,12 @@ def compress_bound(n):
     return int(_lib.call("lz4r_compress_bound", n))
 
 
+def frame_bound(n):
+    """Worst-case bytes of the standard LZ4 frame of n input bytes
+    (lz4r_frame_bound)."""
+    return int(_lib.call("lz4r_frame_bound", n))
+
+
 def _output(d_out, out_cap, device):
     """The caller's d_out, or out_cap new bytes (one at the least)."""
     if d_out is not None:
@@ -105,6 +111,36 @@ class Compressor:
             _call("lz4r_compress_segment_async", *args, 1 if final_shard else 0, stream_arg(stream))
         else:
             _call("lz4r_compress_async", *args, stream_arg(stream))
+
+    # -- standard LZ4 frames ----------------------------------------------
+    def compress_frame_device(self, d_in, n=None, d_out=None, stream=None):
+        """compress_device, for a standard LZ4 frame (what `lz4 -d` and liblz4
+        read): returns (d_out, length), the frame is d_out[:length].  After
+        it block_offsets() raises: a frame has no per-block arrays."""
+        import torch
+        n = d_in.numel() if n is None else n
+        if d_out is None:
+            d_out = torch.empty(frame_bound(n), dtype=torch.uint8, device=d_in.device)
+        got = c_size_t(0)
+        _call("lz4r_compress_frame_device", self._h, d_in, n, d_out, d_out.numel(), byref(got),
+              stream_arg(stream))
+        return d_out, got.value
+
+    def compress_frame_async(self, d_in, n, d_out, d_len, stream=None):
+        """compress_async, for a standard LZ4 frame: enqueue only (capturable
+        into a graph); the length, or the need when it exceeds d_out.numel(),
+        lands in d_len (read it with async_length)."""
+        _call("lz4r_compress_frame_async", self._h, d_in, n, d_out, d_out.numel(), d_len,
+              stream_arg(stream))
+
+    def compress_frame(self, data):
+        """bytes -> the bytes of a standard LZ4 frame."""
+        import torch
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        if buf.size < BLOCK:
+            raise InputTooSmall(_lib.LZ4R_ERR_TOO_SMALL, "compress_frame")
+        d_out, length = self.compress_frame_device(torch.from_numpy(buf.copy()).cuda())
+        return d_out[:length].cpu().numpy().tobytes()
 
     @staticmethod
     def async_length(d_len):
@@ -184,6 +220,39 @@ def compress(data):
     got = c_size_t(0)
     _call("lz4r_compress", buf, n, out, cap, byref(got))
     return out[:got.value].tobytes()
+
+
+def compress_frame(data):
+    """One-shot host API: `data` as a standard LZ4 frame (lz4r_compress_frame)."""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    n = buf.size
+    if n < BLOCK:
+        raise InputTooSmall(_lib.LZ4R_ERR_TOO_SMALL, "lz4r_compress_frame")
+    cap = frame_bound(n)
+    out = np.empty(cap, dtype=np.uint8)
+    got = c_size_t(0)
+    _call("lz4r_compress_frame", buf, n, out, cap, byref(got))
+    return out[:got.value].tobytes()
+
+
+def decompress_frame(frame_bytes, cap=None):
+    """Exact host decoder of standard LZ4 frames (lz4r_frame_decompress): the
+    library's own or any other writer's, one or several concatenated.  cap:
+    the room for the output; by default it grows to what the decoder asks for.
+    Raises Lz4Error(-6) on a malformed frame, Lz4Error(-3) when a given cap
+    is too small."""
+    buf = np.frombuffer(bytes(frame_bytes), dtype=np.uint8)
+    room = 4 * buf.size + 65536 if cap is None else cap
+    while True:
+        out = np.empty(max(room, 1), dtype=np.uint8)
+        got = c_size_t(0)
+        rc = _lib.call("lz4r_frame_decompress", buf, buf.size, out, room, byref(got))
+        if rc == _lib.LZ4R_ERR_CAPACITY and cap is None:
+            room = max(got.value, 2 * room)
+            continue
+        if rc:
+            _raise(rc, "lz4r_frame_decompress")
+        return out[:got.value].tobytes()
 
 
 def decompress(stream, cap=None):

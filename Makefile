@@ -4,7 +4,7 @@
 #   lz4-jpeg_amd/lz4jpeg/liblz4jpeg.so   product C-ABI library (HIP kernels)
 #   lz4-jpeg_amd/bin/LZ4_seq, JPEG_seq    drop-in executables (file contract),
 #                                         also as LZ4_seq.exe / JPEG_seq.exe
-#   lz4-jpeg_amd/bin/LZ4_frame            file -> standard .lz4 frame on the GPU, -d back on the host (also LZ4_frame.exe)
+#   lz4-jpeg_amd/bin/LZ4_frame            file -> standard .lz4 frame on the GPU, -D back on the GPU, -d on the host (also LZ4_frame.exe)
 #   lz4-jpeg_amd/bin/JPEG_dec             coefficients.jpr -> PNG (also JPEG_dec.exe)
 #   lz4-jpeg_amd/bin/JPEG_sel             images or tile windows of a .jpr -> a new .jpr (also JPEG_sel.exe)
 #   oracle/liboracle.so (+ oracle/_ref)   test-only CPU checker
@@ -41,11 +41,12 @@ HDRS    := include/lz4r.h include/jpegr.h include/lz4jpeg_compat.h include/lz4jp
            $(CSRC)/lz4r_tiles.h $(CSRC)/lz4r_matches.h $(CSRC)/lz4r_scan.h $(CSRC)/lz4r_emit.h \
            $(CSRC)/lz4r_frame.h $(HOST)/lz4f_xxh32.h \
            $(CSRC)/lz4r_dec_layout.h $(CSRC)/lz4r_dec_parse.h $(CSRC)/lz4r_dec_blocks.h \
-           $(CSRC)/lz4r_dec_bare.h $(CSRC)/lz4r_dec_read.h $(CSRC)/jpegr_pack_common.h \
+           $(CSRC)/lz4r_dec_bare.h $(CSRC)/lz4r_dec_read.h $(CSRC)/lz4r_scratch.h \
+           $(CSRC)/lz4f_parse.h $(CSRC)/lz4f_dec.h $(CSRC)/jpegr_pack_common.h \
            $(CSRC)/jpegr_entropy_common.h $(CSRC)/jpegr_decode_common.h $(CSRC)/jpegr_crop.h \
            $(CSRC)/jpegr_pixel.h $(CSRC)/jpegr_dct.h $(CSRC)/jpegr_recon.h $(CSRC)/jpegr_tensor_elem.h \
            $(CSRC)/jpegr_resize.h $(CSRC)/jpegr_dataset.h
-OBJS    := $(B)/lz4r.o $(B)/lz4r_gpudec.o $(B)/lz4r_read.o $(B)/jpegr.o $(B)/jpegr_blocks.o \
+OBJS    := $(B)/lz4r.o $(B)/lz4r_gpudec.o $(B)/lz4f_gpudec.o $(B)/lz4r_read.o $(B)/jpegr.o $(B)/jpegr_blocks.o \
            $(B)/jpegr_entropy.o $(B)/jpegr_pack.o $(B)/jpegr_stream.o $(B)/jpegr_stream_enc.o \
            $(B)/jpegr_thumb.o $(B)/jpegr_select.o $(B)/jpegr_resize.o \
            $(B)/synth.o $(B)/synth_dev.o \
@@ -150,7 +151,9 @@ SAN_FLAGS := -O1 -g -ffp-contract=off -fno-omit-frame-pointer \
 # sanitize_main.c's C++ siblings, whichever the tests directory holds
 # (bare_layout.cpp: the decoder's scratch layout; csrc/lz4r_dec_layout.h is
 # plain host C++), each compiled to an object of its own and linked in
-SAN_CXX_OBJ := $(patsubst tests/sanitize/%.cpp,build/san_%.o,$(wildcard tests/sanitize/*.cpp))
+# (frame_dev_main.cpp is a program of its own: sanitize-frame-dev below)
+SAN_CXX_OBJ := $(patsubst tests/sanitize/%.cpp,build/san_%.o,\
+                 $(filter-out tests/sanitize/frame_dev_main.cpp,$(wildcard tests/sanitize/*.cpp)))
 
 build/san_%.o: tests/sanitize/%.cpp $(CSRC)/lz4r_dec_layout.h include/lz4r.h
 	@mkdir -p build
@@ -170,6 +173,21 @@ build/sanitize_frame: tests/sanitize/frame_main.c $(HOST)/lz4f_decode.c $(HOST)/
 	@mkdir -p build
 	$(CC) $(SAN_FLAGS) -std=gnu11 -Wall -o $@ tests/sanitize/frame_main.c $(HOST)/lz4f_decode.c
 
+# ASan + UBSan build of what the GPU frame decoder's kernels parse with
+# (csrc/lz4f_parse.h, compiled for the host) against host/lz4f_decode.c,
+# driven by tests/sanitize/frame_dev_main.cpp; tests/test_sanitize_frame_dev.py
+sanitize-frame-dev: build/sanitize_frame_dev
+	./build/sanitize_frame_dev
+
+build/san_lz4f_decode.o: $(HOST)/lz4f_decode.c $(HOST)/lz4f_xxh32.h include/lz4r.h
+	@mkdir -p build
+	$(CC) $(SAN_FLAGS) -std=gnu11 -Wall -c $< -o $@
+
+build/sanitize_frame_dev: tests/sanitize/frame_dev_main.cpp build/san_lz4f_decode.o \
+                          $(CSRC)/lz4f_parse.h $(HOST)/lz4f_xxh32.h include/lz4r.h
+	@mkdir -p build
+	$(CXX) $(SAN_FLAGS) -std=c++17 -Wall -o $@ tests/sanitize/frame_dev_main.cpp build/san_lz4f_decode.o
+
 # micro-benchmarks: SIMD issue rates (tools/issue.sh) and LDS access costs
 tools: tools/ab/valu_rate tools/ab/lds_rate
 
@@ -185,7 +203,7 @@ clean:
 	rm -rf $(B) $(BIN) $(LIB) build
 	$(MAKE) -C oracle clean
 
-.PHONY: all lib bin oracle tools chunk12 thumb-alt sanitize sanitize-frame clean
+.PHONY: all lib bin oracle tools chunk12 thumb-alt sanitize sanitize-frame sanitize-frame-dev clean
 
 # `make -s print-HIPFLAGS`: a variable's value (tests/test_isa.py builds with the product flags)
 print-%:

@@ -303,6 +303,57 @@ int lz4r_compress_frame(const uint8_t *in, size_t n, uint8_t *out, size_t cap,
 int lz4r_frame_decompress(const uint8_t *in, size_t in_len, uint8_t *out,
                           size_t cap, size_t *out_len);
 
+/* flags of lz4r_frame_decompress_device / lz4r_frame_decompress_gpu */
+#define LZ4R_FRAME_NO_CONTENT_CHECKSUM 1u   /* do not verify a frame's content checksum */
+
+/* Decode standard LZ4 frames on the GPU (csrc/lz4f_gpudec.hip), enqueued on
+ * `stream`, which the call synchronises.  d_in (in_len bytes) and d_out
+ * (out_cap bytes) are device pointers of any alignment.
+ * Accepts every frame lz4r_frame_decompress accepts -- independent and linked
+ * blocks, stored blocks, content size present or absent, block maxima from
+ * 64 KiB to 4 MiB, concatenated frames -- and verifies what it verifies: the
+ * header checksum, block checksums when flagged, the content size when
+ * present, and the content checksum when flagged unless flags has
+ * LZ4R_FRAME_NO_CONTENT_CHECKSUM (as liblz4's skipChecksums).  Everything
+ * the host decoder calls corrupt is LZ4R_ERR_CORRUPT here (skippable and
+ * legacy magics, dictionary IDs and reserved bits among it; in_len 0 too): for
+ * every input the return code equals lz4r_frame_decompress's, and on LZ4R_OK
+ * so do the bytes and *out_len.
+ * Independent and stored blocks decode in parallel, a wave each; a linked
+ * frame is one serial chain (frames still run side by side); a content
+ * checksum is serial over its frame's decoded bytes (xxh32 has no combine
+ * step), one wave per frame.
+ * LZ4R_ERR_CAPACITY when the frames decode to more than out_cap bytes: then
+ * *out_len is the exact decoded length of all frames, known from the blocks'
+ * tokens before anything is decoded, and nothing is written.  A frame that is
+ * malformed in its headers, size words, block checksums, token streams or
+ * content sizes is LZ4R_ERR_CORRUPT whatever out_cap is; a match distance
+ * beyond its window or a wrong content checksum is found only by decoding,
+ * which needs the room: with too small an out_cap such a frame is
+ * LZ4R_ERR_CAPACITY (nothing is written), and LZ4R_ERR_CORRUPT once the
+ * capacity it names is given.
+ * Whatever the bytes say, nothing outside d_in[0, in_len) is read and
+ * nothing outside d_out[0, out_cap) and the call's own scratch is written; a
+ * block that fails may leave unspecified bytes in its own output range only.
+ * LZ4R_ERR_ARG, before any HIP call, for a NULL d_in or out_len, or a NULL
+ * d_out with out_cap > 0.
+ * Scratch: a stream-ordered allocation from the per-device pool the
+ * bare-stream decoder keeps: 28 bytes per data block and 40 per frame, with
+ * room for in_len / 1024 + 4096 blocks and in_len / 65536 + 64 frames (about
+ * in_len / 36 + 120 KB: 30 MB for a 1 GiB input); an input with more blocks
+ * or frames than that is walked a second time into an index of exactly their
+ * number.
+ * Host read-backs: two per call, for every input -- the walk's block and frame
+ * counts, then the total length with the verdict.  Whether the output fits is
+ * decided on the device between them. */
+int lz4r_frame_decompress_device(const void *d_in, size_t in_len, void *d_out,
+                                 size_t out_cap, size_t *out_len,
+                                 unsigned flags, void *stream);
+
+/* Host-buffer form of lz4r_frame_decompress_device (copies in and out). */
+int lz4r_frame_decompress_gpu(const uint8_t *in, size_t in_len, uint8_t *out,
+                              size_t cap, size_t *out_len, unsigned flags);
+
 /* Synchronise `stream` and report whether the last compress call on ctx met
  * a corrupt bucket head in lz4_tiles' LDS index (a head that is neither empty
  * nor an earlier position of the block: never on a sound LDS; the walk ends

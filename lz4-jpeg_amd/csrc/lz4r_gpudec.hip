@@ -36,6 +36,7 @@
 
 #include "../../include/lz4r.h"
 #include "wave64.h"
+#include "lz4r_scratch.h"
 #include "lz4r_dec_layout.h"
 #include "lz4r_dec_parse.h"
 #include "lz4r_dec_blocks.h"
@@ -85,9 +86,18 @@ hipMemPool_t scratch_pool() {
   return p;
 }
 
-hipError_t scratch_alloc(void **ptr, size_t bytes, hipStream_t s) {
+}  // namespace
+
+// (declared in lz4r_scratch.h: the frame decoder, lz4f_gpudec.hip, allocates from the same pool)
+hipError_t lz4r_scratch_alloc(void **ptr, size_t bytes, hipStream_t s) {
   hipMemPool_t p = scratch_pool();
   return p ? hipMallocFromPoolAsync(ptr, bytes, p, s) : hipMallocAsync(ptr, bytes, s);
+}
+
+namespace {
+
+hipError_t scratch_alloc(void **ptr, size_t bytes, hipStream_t s) {
+  return lz4r_scratch_alloc(ptr, bytes, s);
 }
 
 // the control words read back after the decode -> the call's return code and

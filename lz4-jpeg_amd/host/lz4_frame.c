@@ -5,6 +5,7 @@
  *                              frame reader
  *   LZ4_frame -d in.lz4 out    decode on the host (lz4r_frame_decompress): any
  *                              standard frame, or several concatenated
+ *   LZ4_frame -D in.lz4 out    the same on the GPU (lz4r_frame_decompress_gpu)
  * Any error is one line on stderr and exit status 1.
  */
 #include <stdio.h>
@@ -27,8 +28,10 @@ static void write_file(const char *path, const uint8_t *data, size_t len) {
 }
 
 int main(int argc, char **argv) {
-  const int decode = argc == 4 && strcmp(argv[1], "-d") == 0;
-  if (!decode && argc != 3) fail("usage: LZ4_frame in out.lz4 | LZ4_frame -d in.lz4 out", NULL);
+  const int gpu = argc == 4 && strcmp(argv[1], "-D") == 0;
+  const int decode = gpu || (argc == 4 && strcmp(argv[1], "-d") == 0);
+  if (!decode && argc != 3)
+    fail("usage: LZ4_frame in out.lz4 | LZ4_frame -d in.lz4 out | LZ4_frame -D in.lz4 out", NULL);
   const char *src = argv[decode ? 2 : 1], *dst = argv[decode ? 3 : 2];
   uint8_t *in = NULL;
   size_t n = 0;
@@ -36,7 +39,16 @@ int main(int argc, char **argv) {
   uint8_t *out = NULL;
   size_t got = 0;
   int rc;
-  if (decode) {
+  if (gpu) {
+    /* with no room the decoder names the decoded length, exactly */
+    rc = lz4r_frame_decompress_gpu(in, n, NULL, 0, &got, 0);
+    if (rc == LZ4R_ERR_CAPACITY) {
+      const size_t cap = got;
+      out = (uint8_t *)malloc(cap);
+      if (!out) fail("out of memory", NULL);
+      rc = lz4r_frame_decompress_gpu(in, n, out, cap, &got, 0);
+    }
+  } else if (decode) {
     /* the decoder names the length needed so far: grow until it fits */
     size_t cap = 4 * n + 65536;
     for (;;) {

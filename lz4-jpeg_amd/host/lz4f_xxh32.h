@@ -15,6 +15,14 @@
 #define LZ4F_P4 668265263u
 #define LZ4F_P5 374761393u
 
+/* every function here also compiles as device code of a HIP source (the GPU
+ * frame decoder's checksums, csrc/lz4f_dec.h, are these functions) */
+#if defined(__HIPCC__)
+#define LZ4F_FN __host__ __device__ static inline
+#else
+#define LZ4F_FN static inline
+#endif
+
 typedef struct lz4f_xxh32_state {
   uint32_t v[4];
   uint8_t buf[16];
@@ -23,17 +31,17 @@ typedef struct lz4f_xxh32_state {
   uint32_t seed;
 } lz4f_xxh32_state;
 
-static inline uint32_t lz4f_rotl(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
+LZ4F_FN uint32_t lz4f_rotl(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
 
-static inline uint32_t lz4f_le32(const uint8_t *p) {
+LZ4F_FN uint32_t lz4f_le32(const uint8_t *p) {
   return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
 }
 
-static inline uint32_t lz4f_round(uint32_t acc, uint32_t lane) {
+LZ4F_FN uint32_t lz4f_round(uint32_t acc, uint32_t lane) {
   return lz4f_rotl(acc + lane * LZ4F_P2, 13) * LZ4F_P1;
 }
 
-static inline void lz4f_xxh32_init(lz4f_xxh32_state *s, uint32_t seed) {
+LZ4F_FN void lz4f_xxh32_init(lz4f_xxh32_state *s, uint32_t seed) {
   s->v[0] = seed + LZ4F_P1 + LZ4F_P2;
   s->v[1] = seed + LZ4F_P2;
   s->v[2] = seed;
@@ -43,11 +51,11 @@ static inline void lz4f_xxh32_init(lz4f_xxh32_state *s, uint32_t seed) {
   s->seed = seed;
 }
 
-static inline void lz4f_stripe(lz4f_xxh32_state *s, const uint8_t *p) {
+LZ4F_FN void lz4f_stripe(lz4f_xxh32_state *s, const uint8_t *p) {
   for (int i = 0; i < 4; ++i) s->v[i] = lz4f_round(s->v[i], lz4f_le32(p + 4 * i));
 }
 
-static inline void lz4f_xxh32_update(lz4f_xxh32_state *s, const uint8_t *p, size_t n) {
+LZ4F_FN void lz4f_xxh32_update(lz4f_xxh32_state *s, const uint8_t *p, size_t n) {
   s->total += n;
   if (s->nbuf) {
     size_t take = 16 - s->nbuf;
@@ -67,7 +75,7 @@ static inline void lz4f_xxh32_update(lz4f_xxh32_state *s, const uint8_t *p, size
   }
 }
 
-static inline uint32_t lz4f_xxh32_digest(const lz4f_xxh32_state *s) {
+LZ4F_FN uint32_t lz4f_xxh32_digest(const lz4f_xxh32_state *s) {
   uint32_t h = s->total >= 16 ? lz4f_rotl(s->v[0], 1) + lz4f_rotl(s->v[1], 7) +
                                     lz4f_rotl(s->v[2], 12) + lz4f_rotl(s->v[3], 18)
                               : s->seed + LZ4F_P5;
@@ -84,7 +92,7 @@ static inline uint32_t lz4f_xxh32_digest(const lz4f_xxh32_state *s) {
   return h;
 }
 
-static inline uint32_t lz4f_xxh32(const uint8_t *p, size_t n, uint32_t seed) {
+LZ4F_FN uint32_t lz4f_xxh32(const uint8_t *p, size_t n, uint32_t seed) {
   lz4f_xxh32_state s;
   lz4f_xxh32_init(&s, seed);
   lz4f_xxh32_update(&s, p, n);

@@ -38,6 +38,10 @@ SIGNATURES = [
                                         _vp]),
     ("lz4r_compress_frame", _i, [_vp, _c_size, _vp, _c_size, ctypes.POINTER(_c_size)]),
     ("lz4r_frame_decompress", _i, [_vp, _c_size, _vp, _c_size, ctypes.POINTER(_c_size)]),
+    ("lz4r_frame_decompress_device", _i, [_vp, _c_size, _vp, _c_size, ctypes.POINTER(_c_size),
+                                          ctypes.c_uint, _vp]),
+    ("lz4r_frame_decompress_gpu", _i, [_vp, _c_size, _vp, _c_size, ctypes.POINTER(_c_size),
+                                       ctypes.c_uint]),
     ("lz4r_decompress_device", _i, [_vp, _c_size, _vp, _c_size, _vp, _c_size, _vp, _vp]),
     ("lz4r_decompress_stream_device", _i, [_vp, _c_size, _vp, _c_size, ctypes.POINTER(_c_size),
                                            _vp]),
@@ -230,5 +234,6 @@ LZ4R_ERR_CAPACITY = -3
 LZ4R_ERR_HIP = -4
 LZ4R_ERR_NOMEM = -5
 LZ4R_ERR_CORRUPT = -6
+LZ4R_FRAME_NO_CONTENT_CHECKSUM = 1
 LZ4R_BLOCK = 300
 LZ4R_BLOCK_BOUND = 1152

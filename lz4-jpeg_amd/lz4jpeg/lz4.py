@@ -255,6 +255,49 @@ def decompress_frame(frame_bytes, cap=None):
         return out[:got.value].tobytes()
 
 
+def decompress_frame_device(d_frame, length=None, cap=None, d_out=None, verify_content=True,
+                            stream=None):
+    """GPU decoder of standard LZ4 frames (lz4r_frame_decompress_device): the
+    first `length` bytes of the uint8 tensor d_frame, one frame or several
+    concatenated, this library's or any other writer's.  Returns (d_out, n):
+    the decoded bytes are d_out[:n].  cap: the room for the output (d_out's
+    size when d_out is given); with neither, one call with no room asks for
+    the decoded length, which is then allocated and decoded into.
+    verify_content=False skips the frames' content checksums.  Raises
+    Lz4Error(-6) on a malformed frame, Lz4Error(-3) when a given cap or d_out
+    is too small.  Synchronises `stream`."""
+    import torch
+    length = d_frame.numel() if length is None else length
+    flags = 0 if verify_content else _lib.LZ4R_FRAME_NO_CONTENT_CHECKSUM
+    got = c_size_t(0)
+    if cap is None and d_out is None:
+        rc = _lib.call("lz4r_frame_decompress_device", d_frame, length, None, 0, byref(got), flags,
+                       stream_arg(stream))
+        if rc not in (_lib.LZ4R_OK, _lib.LZ4R_ERR_CAPACITY):
+            _raise(rc, "lz4r_frame_decompress_device")
+        if rc == _lib.LZ4R_OK:                           # frames of no bytes at all
+            return torch.empty(0, dtype=torch.uint8, device=d_frame.device), 0
+        cap = got.value
+    elif cap is None:
+        cap = d_out.numel()
+    d_out = _output(d_out, cap, d_frame.device)
+    _call("lz4r_frame_decompress_device", d_frame, length, d_out, cap, byref(got), flags,
+          stream_arg(stream))
+    return d_out, got.value
+
+
+def decompress_frame_gpu(frame_bytes, verify_content=True):
+    """Host bytes of standard LZ4 frames -> the decoded bytes, by the GPU
+    decoder (decompress_frame_device after a copy in, then a copy out)."""
+    import torch
+    buf = np.frombuffer(bytes(frame_bytes), dtype=np.uint8)
+    if buf.size == 0:
+        _raise(_lib.LZ4R_ERR_CORRUPT, "lz4r_frame_decompress_device")
+    d_out, n = decompress_frame_device(torch.from_numpy(buf.copy()).cuda(),
+                                       verify_content=verify_content)
+    return d_out[:n].cpu().numpy().tobytes()
+
+
 def decompress(stream, cap=None):
     """Exact host decoder (lz4r_decompress): framed stream bytes -> original
     bytes.  Replaces LZ4_decode (LZ4.c:1038-1121); raises Lz4Error(-6) on a
